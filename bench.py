@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload lj|fcm]
+    python bench.py --gpus N --steps K --warmup W [--workload lj|fcm] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, melt the input (--equilibrate), warm up, time exactly --steps steps once,
+write the outputs (--dump-outputs) and print the line.  `--full` adds everything else the benchmark measures or checks: the timed
+block repeated until --min-timed-seconds of GPU work (--repeats 0), the FCM / FCM C5 / PSE lines and the reference benchmark's
+configurations beside the LJ one (--workload both), the CPU baselines, and at N > 1 the preflight, the FCM lines and the
+strong-scaling line.
+
+--dump-outputs DIR: after the timed steps, what the timed path's last step left for its caller, in particle-id order, as
+DIR/<name>.npy (float32): LJ pos (N x 4: xyz + type), vel (N x 3), force (N x 4); FCM / PSE pos (N x 4).  Single-domain runs only.
 
 Workload "lj" (default; BASELINE.json configs[2], the configuration the metric is quoted on):
   1e6 Lennard-Jones particles, rho* = 0.8 (L = 107.7217345 -> 43^3 cells), r_c = 2.5 sigma,
@@ -63,6 +72,18 @@ def emit_result(obj):
         sys.stdout.flush()
     else:
         os.write(_RESULT_FD, line)
+
+
+def dump_outputs(outdir, pd, names):
+    """--dump-outputs: the ParticleData arrays `names` (pos / vel / force) as outdir/<name>.npy, float32, rows in particle-id order (a sort
+    inside the run reorders memory, not the particles)."""
+    os.makedirs(outdir, exist_ok=True)
+    ids = pd.id.long().cpu().numpy()
+    for name in names:
+        a = {"pos": pd.getPos, "vel": pd.getVel, "force": pd.getForce}[name]().float().cpu().numpy()
+        out = np.empty_like(a)
+        out[ids] = a
+        np.save(os.path.join(outdir, name + ".npy"), out)
 
 
 def _barrier(dist):
@@ -243,7 +264,7 @@ def fcm_setup(hip, n, cells, L, seed, T=1.0, dt=0.01):
     return pd, integ, pos, force
 
 
-def run_fcm(hip, args, world, rank, dist):
+def run_fcm(hip, args, world, rank, dist, dump_dir=None):
     n, cells, L = 100_000, [128, 128, 128], 128.0
     pd, integ, pos, force = fcm_setup(hip, n, cells, L, seed=1234 + rank)
     if args.fcm_sort:
@@ -268,6 +289,8 @@ def run_fcm(hip, args, world, rank, dist):
     if _reducing(dist):
         el = _allreduce(dist, [el], "MAX")[0]
     assert np.isfinite(pd.getPos().cpu().numpy()).all()
+    if dump_dir:
+        dump_outputs(dump_dir, pd, ["pos"])
     ms = el / args.fcm_steps * 1e3
     gbs = fcm_bytes_per_step(n, cells) / (ms * 1e-3) / 1e9
     out = {"metric": "FCM-BDHI steps/s @128^3 (1e5 particles, tol 1e-3, T=1)", "value": world * args.fcm_steps / el,
@@ -278,7 +301,7 @@ def run_fcm(hip, args, world, rank, dist):
                         "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
                         "traffic": read_traffic("traffic_fcm_step.json"),
                         "algorithmic_bytes_per_step": fcm_bytes_per_step(n, cells)}}
-    if world == 1:   # the deterministic step (T = 0: no Fourier-space noise) beside the thermal one
+    if world == 1 and args.full:   # the deterministic step (T = 0: no Fourier-space noise) beside the thermal one
         pd0, integ0, _, _ = fcm_setup(hip, n, cells, L, seed=1234 + rank, T=0.0)
         for _ in range(args.fcm_warmup):
             integ0.forwardTime()
@@ -474,7 +497,7 @@ def _timed(fn, reps, warm=3):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
-def run_pse(hip, args):
+def run_pse(hip, args, dump_dir=None):
     """BDHI::EulerMaruyama<BDHI::PSE>: N = 1e5, L = 128, a = 1, psi = 0.5 (PSE/utils.cuh:17-24 default), tolerance 1e-3, T = 1, dt = 0.01,
     fixed N(0,1) forces.  One step = far field (spread, FFT, sheared Hasimoto-split operator + noise, FFT, gather) + near-field M F (one
     sparse product over the cell list, rc = sqrt(-ln tol) / psi = 5.26) + near-field noise by Lanczos (k products + the recurrence)
@@ -513,6 +536,8 @@ def run_pse(hip, args):
     ms = float(np.median(block_ms))
     steps = nblocks * per_block
     assert np.isfinite(pd.getPos().cpu().numpy()).all()
+    if dump_dir:
+        dump_outputs(dump_dir, pd, ["pos"])
     stats = (C.c_longlong * 4)()
     check(lib.uammd_pse_near_list_stats(pse.near, stats))
     # the parts, each on its own (same state)
@@ -951,9 +976,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--min-timed-seconds", type=float, default=12.0, help="with --repeats 0: repeat the timed --steps block until the LJ headline has timed at least this much GPU work")
-    ap.add_argument("--repeats", type=int, default=0, help="how many times the timed --steps block is run (0 = as many as --min-timed-seconds asks, at least 10 for blocks of <= 100 steps); "
-                                                           "value / ms_per_step are the median block, the spread is reported")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline (see the module docstring); off: the plain run "
+                                                        "times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--min-timed-seconds", type=float, default=12.0, help="with --full and --repeats 0: repeat the timed --steps block until the LJ headline has timed at least this much GPU work")
+    ap.add_argument("--repeats", type=int, default=0, help="how many times the timed --steps block is run (0 = once, or with --full as many as --min-timed-seconds asks, at "
+                                                           "least 10 for blocks of <= 100 steps); value / ms_per_step are the median block, the spread is reported")
     ap.add_argument("--equilibrate", type=int, default=2000, help="untimed steps that melt the lattice before warm-up (part of the synthetic input; 2000 = the warm-up of the reference's benchmark.cu:129-157, SURVEY 8d)")
     ap.add_argument("--workload", default="both", choices=["lj", "fcm", "both", "pse"])
     ap.add_argument("--pse-steps", type=int, default=50)
@@ -982,6 +1010,9 @@ def main():
                     "a stage that runs out prints a JSON line with an `error` field and exits instead of hanging")
     ap.add_argument("--max-seconds", type=float, default=1500.0, help="N > 1: wall-clock budget of the timed workloads")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.force_distributed):
+        print("bench.py: --dump-outputs is for single-domain runs (--gpus 1, no --force-distributed)", file=sys.stderr)
+        sys.exit(2)
 
     same_device = os.environ.get("UAMMD_BENCH_SAME_DEVICE") == "1"
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1095,7 +1126,7 @@ def main():
             comm_info["abi_comm_error"] = err
         print(f"[bench rank {rank}] {comm_info['devices'][rank] if world > 1 else comm_info['devices']}; RCCL {comm_info.get('rccl_version')}; "
               f"messages through {TRANSPORT}", file=sys.stderr, flush=True)
-        if not args.no_preflight:
+        if args.full and not args.no_preflight:
             stage("preflight: small slab runs against the single-domain classes", args.stage_seconds)
             perr, rep_ = None, None
             try:
@@ -1111,17 +1142,20 @@ def main():
         if world > 1:
             print("bench.py: the PSE line is single-GPU (the near field shards like path A, the far field like path B)", file=sys.stderr)
             sys.exit(2)
-        out = run_pse(hip, args)
-        if not args.no_cpu_baseline:
+        out = run_pse(hip, args, dump_dir=args.dump_outputs)
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_pse(args.cpu_pse_steps)
         out.update({"n_gpus": 1, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic"})
         emit_result(out)
         return
     if args.workload == "fcm":
-        out = (run_fcm_distributed if (world > 1 or args.force_distributed) else run_fcm)(hip, args, world, rank, dist)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if world > 1 or args.force_distributed:
+            out = run_fcm_distributed(hip, args, world, rank, dist)
+        else:
+            out = run_fcm(hip, args, world, rank, dist, dump_dir=args.dump_outputs)
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_fcm(args.cpu_fcm_steps)
-        if not args.no_c5:
+        if args.full and not args.no_c5:
             _settle()
             out["fcm_c5"] = run_fcm_c5(hip, args, world, rank, dist)
         out.update({"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -1151,11 +1185,11 @@ def main():
             "roofline": {"bound": "valu", "kernel": "LJ traversal (k_lj_tile4), owned + ghost particles",
                          "achieved": achieved_tflops, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved_tflops / PEAK_FP32_TFLOPS, "traffic": None, "kernel_ms": k_ms}}
-        if args.workload == "both":
+        if args.workload == "both" and args.full:
             out["fcm"] = run_fcm_distributed(hip, args, world, rank, dist)
             out["fcm_c5"] = run_fcm_c5(hip, args, world, rank, dist)
         out["comm"] = comm_info
-        if world > 1 and os.environ.get("UAMMD_BENCH_NO_STRONG") != "1":
+        if world > 1 and args.full and os.environ.get("UAMMD_BENCH_NO_STRONG") != "1":
             # the STRONG-scaling line beside the weak headline: BASELINE's one 1e6 box over the N GPUs (at N = 1 it IS the single-domain
             # line).  Run LAST and as an optional stage: everything above is complete, and whatever happens here — a rank that raises, a
             # collective that never returns — the line printed is the result so far with the failure noted under "lj_strong".
@@ -1202,9 +1236,9 @@ def main():
     profiled = args.nl == "cell" and os.environ.get("UAMMD_BENCH_NOTIMER") != "1"
     if profiled:
         pf.nl.profile_enable(True)   # start / stop events on the traversal kernel's own dispatch, every launch of the timed region
-    # The timed region is EXACTLY --steps steps between barrier + synchronize on both sides.  A 20-step block is 4 ms of GPU time, so the
-    # block is repeated (each repeat bracketed the same way) and the line reports the MEDIAN block with the spread next to it.
-    # With --repeats 0 (the default) the number of blocks follows the first block's time so that the headline's timed region holds at least
+    # The timed region is EXACTLY --steps steps between barrier + synchronize on both sides.  A plain run times one block; --repeats R
+    # repeats it (each repeat bracketed the same way) and the line reports the MEDIAN block with the spread next to it.
+    # With --full and --repeats 0 the number of blocks follows the first block's time so that the headline's timed region holds at least
     # --min-timed-seconds (12 s: two periods of the sampler the driver reads gpu_busy from) of GPU work whatever --steps is: the driver's --steps 20 is 4 ms per block, 39 ms in ten blocks — too short
     # for anything that samples the GPU from outside (its gpu_busy probe read 0 % in rounds 1-3).
     blocks, done = [], 0
@@ -1224,7 +1258,7 @@ def main():
         if _reducing(dist):
             el = _allreduce(dist, [el], "MAX")[0]
         blocks.append(el)
-        if args.repeats <= 0 and len(blocks) == 1:
+        if args.repeats <= 0 and args.full and len(blocks) == 1:
             nrep = int(min(5000, max(10 if args.steps <= 100 else 1, math.ceil(args.min_timed_seconds / max(el, 1e-6)))))
             if _reducing(dist):
                 nrep = int(_allreduce(dist, [float(nrep)], "MAX")[0])
@@ -1237,6 +1271,8 @@ def main():
 
     pos = pd.getPos().cpu().numpy()
     assert np.isfinite(pos).all(), "non finite positions after the run"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pd, ["pos", "vel", "force"])
     ms_per_step = el / args.steps * 1e3
     if os.environ.get("UAMMD_BENCH_DEBUG") == "1":
         print(f"[debug] LJ timed loop: {el:.4f} s for {args.steps} steps", file=sys.stderr, flush=True)
@@ -1279,7 +1315,7 @@ def main():
                      "frac_of_single_issue_peak": achieved_tflops / (PEAK_FP32_TFLOPS / 2),
                      "hbm_frac_compulsory": BYTES_COMPULSORY_PER_PARTICLE * n / (k_ms * 1e-3) / 1e9 / PEAK_HBM_GBS},
     }
-    if args.workload == "both" and args.nl == "cell" and world == 1:
+    if args.workload == "both" and args.full and args.nl == "cell" and world == 1:
         # the same box with the reference benchmark's neighbour list (examples/misc/benchmark.cu:82-84): extra information,
         # `value` above stays the CellList configuration BASELINE.json names
         del pd, verlet, pf
@@ -1340,7 +1376,7 @@ def main():
                                                        "note": "same box, potential, integrator and sort period with PairForces<LJ, CellList>"}
         del pd4, verlet4, pf4
         _settle()
-    if args.workload == "both":
+    if args.workload == "both" and args.full:
         _settle()
         fcm = run_fcm(hip, args, world, rank, dist)
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -1349,12 +1385,12 @@ def main():
         if not args.no_c5:
             _settle()
             out["fcm_c5"] = run_fcm_c5(hip, args, world, rank, dist)
-    if args.workload == "both" and world == 1:
+    if args.workload == "both" and args.full and world == 1:
         _settle()
         out["pse"] = run_pse(hip, args)
         if not args.no_cpu_baseline:
             out["pse"]["cpu_baseline"] = cpu_baseline_pse(args.cpu_pse_steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_lj(n, L, 1234, args.cpu_sample_steps)
     if rank == 0:
         out["comm"] = comm_info

@@ -265,7 +265,7 @@ def test_bench_strong_scaling_line_on_one_device(world):
         env.pop(k, None)
     n = 131072
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--workload", "lj", "--particles", str(n), "--steps", "40",
-                        "--warmup", "10", "--equilibrate", "60", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "10", "--equilibrate", "60", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert "error" not in line, line
