@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <istream>
+#include <type_traits>
 #include <ostream>
 
 // text form of the vector types: components separated by one blank (utils/printOverloads.h; `out << pos[i]` in
@@ -26,6 +27,12 @@ inline std::ostream &operator<<(std::ostream &out, const ::int3 &f) { return out
 inline std::istream &operator>>(std::istream &in, uammd::real2 &f) { return in >> f.x >> f.y; }
 inline std::istream &operator>>(std::istream &in, uammd::real3 &f) { return in >> f.x >> f.y >> f.z; }
 inline std::istream &operator>>(std::istream &in, uammd::real4 &f) { return in >> f.x >> f.y >> f.z >> f.w; }
+// a stream of a DERIVED type (std::ifstream, std::istringstream: test/Bonds/Bonds.cu reads `lbox` so) would otherwise be as good a match
+// for the runtime's own shift operator template on vector types under hipcc, and the call ambiguous
+template <class S, class V, std::enable_if_t<std::is_base_of<std::istream, S>::value && !std::is_same<S, std::istream>::value &&
+                                             (std::is_same<V, uammd::real2>::value || std::is_same<V, uammd::real3>::value ||
+                                              std::is_same<V, uammd::real4>::value), int> = 0>
+inline std::istream &operator>>(S &in, V &f) { return static_cast<std::istream &>(in) >> f; }
 
 namespace uammd {
 

@@ -134,7 +134,10 @@ int uammd_lj_profile_read(uammd_celllist *h, double *total_ms, long long *launch
  * particles with input index >= n as ghosts of a domain decomposition: they are neighbours of the others but the LJ
  * traversal computes nothing for them (n < 0 turns it off) */
 int uammd_celllist_set_option(uammd_celllist *h, const char *name, int value);
-/* library-wide tunables (none at present; the call is kept for ABI stability and returns an error for unknown names) */
+/* library-wide tunables (measurement switches; an unknown name or a bad value is an error):
+ *   "bonded_baseline" = 1        uammd_bonded_sum runs the reference-shaped kernel (thread per particle, AoS entries, id2index looked up
+ *                                on every step, BondedForces.cu:191-246); 0 (default) the CSR kernels
+ *   "bonded_wave_threshold" = T  rows with more than T entries take the wave-per-row shape (default 32) */
 int uammd_hip_set_tunable(const char *name, int value);
 
 /* ParticleSorter::updateOrderWithCustomHash + applyCurrentOrder building blocks
@@ -892,6 +895,42 @@ int uammd_bdhi_cholesky_mf_f64(uammd_bdhi_cholesky_f64 *h, const double *d_pos, 
                                double *d_MF, void *stream);
 int uammd_bdhi_cholesky_bdw_f64(uammd_bdhi_cholesky_f64 *h, const double *d_pos, const int *d_index, const double *d_radius, double *d_BdW,
                                 void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Bonded interactions.  Replaces BondedForces<BondType, particlesPerBond> (Interactor/BondedForces.{cuh,cu}),
+ * AngularBondedForces.cuh and TorsionalBondedForces.cuh for the built-in kinds.  Every particle with bonds sums, in registration
+ * order, each bond it is a member of and adds the result to its own force / energy / virial: no atomics, the same bits on every run.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_bonded uammd_bonded; /* opaque; owns the CSR rows of one bond set */
+/* kinds and their BondInfo, two floats in the reference's struct order (the bond file gives the same two numbers as "k p0"):
+ *   0 Harmonic {k, r0}      1 FENE {r0, k}      (2 members; fixed points allowed)
+ *   2 Angular {ang0, k}     (3 members)
+ *   3 Torsional {phi0, k}   4 FourierLAMMPS {phi0, kdih}   (4 members) */
+#define UAMMD_BOND_HARMONIC 0
+#define UAMMD_BOND_FENE 1
+#define UAMMD_BOND_ANGULAR 2
+#define UAMMD_BOND_TORSIONAL 3
+#define UAMMD_BOND_FOURIER_LAMMPS 4
+int uammd_bonded_create(uammd_bonded **out);
+int uammd_bonded_destroy(uammd_bonded *h);
+/* Host logic only (no GPU): BondProcessor + buildBondList (BondedForces.cu:35-74,109-137).  ids[nbonds * particlesPerBond] are
+ * particle ids, negative = a fixed point (registers nothing).  Rows are the particles with bonds in ascending id; row r is
+ * rowId[r] and its entries are entryBond[rowStart[r] .. rowStart[r+1]), the bonds it belongs to in registration order.  Sizes:
+ * rowId, rowStart - 1 and entryBond at most nbonds * particlesPerBond; any output may be NULL (the counts alone). */
+int uammd_bonded_build_rows(int particlesPerBond, int nbonds, const int *ids, int *nrows, int *nentries, int *rowId, int *rowStart,
+                            int *entryBond);
+/* Upload one bond set (host arrays): ids[nbonds * members] (a negative id -(j+1) names fixedPoints[j], real4[nfixed], 2-member kinds
+ * only), info[2 * nbonds] (BondInfo per bond, struct order above) and the box the kind applies the minimum image in.  The rows are
+ * laid out here and split between the two traversal shapes by their length.  Synchronous. */
+int uammd_bonded_upload(uammd_bonded *h, int kind, int nbonds, const int *ids, const float *info, int nfixed, const float *fixedPoints,
+                        const float L[3], const int periodic[3]);
+/* After an upload and after every ParticleData reorder: d_id2index[numberParticles] (ParticleData::getIdOrderedIndices) maps the
+ * stored ids to current indices; the handle keeps its own copy. */
+int uammd_bonded_refresh(uammd_bonded *h, const int *d_id2index, int numberParticles, void *stream);
+/* Interactor::sum: force real4[N] += , energy[N] += , virial[N] += , each NULL when not requested (Interactor::Computables). */
+int uammd_bonded_sum(uammd_bonded *h, const float *d_pos, float *d_force, float *d_energy, float *d_virial, void *stream);
+/* the CSR as laid out: rows, entries and how many rows each shape takes under the current "bonded_wave_threshold" */
+int uammd_bonded_get_shape(uammd_bonded *h, int *rows, int *entries, int *laneRows, int *waveRows);
 
 #ifdef __cplusplus
 }

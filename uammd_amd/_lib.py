@@ -132,6 +132,13 @@ SIGNATURES = {
     "uammd_hip_device_count": (_i, [C.POINTER(_i)]),
     "uammd_hip_set_device": (_i, [_i]),
     "uammd_hip_set_tunable": (_i, [C.c_char_p, _i]),
+    "uammd_bonded_create": (_i, [C.POINTER(_vp)]),
+    "uammd_bonded_destroy": (_i, [_vp]),
+    "uammd_bonded_build_rows": (_i, [_i, _i, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp]),
+    "uammd_bonded_upload": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _f3, _i3]),
+    "uammd_bonded_refresh": (_i, [_vp, _vp, _i, _vp]),
+    "uammd_bonded_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "uammd_bonded_get_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "uammd_celllist_create": (_i, [C.POINTER(_vp)]),
     "uammd_celllist_destroy": (_i, [_vp]),
     "uammd_celllist_create_grid": (_i, [_f3, _i3, _f3, _i3, _f3, _i3]),

@@ -24,6 +24,7 @@
 #include <string>
 
 namespace uammd_hip {
+int bonded_set_tunable(const char *name, int value);  // bonded.hip
 
 // ---- two-phase pair evaluation ---------------------------------------------------------------------
 // Only ~15 % of the candidate pairs of a 27-cell walk are inside the cut-off (4.19 rc^3 of 27 rc^3),
@@ -641,7 +642,7 @@ int uammd_lj_process_pair_parameters(float cutOff, float sigma, float epsilon, i
 }
 
 int uammd_hip_set_tunable(const char *name, int value) {
-  (void)value;
+  if (name && bonded_set_tunable(name, value) == 0) return 0;
   set_last_error("uammd_hip_set_tunable: unknown tunable or bad value");
   return -1;
 }
