@@ -20,9 +20,8 @@
 // single precision by construction and stays that way: `real` = float is UAMMD's default and the benchmarked configuration.
 #include "celllist.hpp"
 #include "ibm.hpp"
+#include "rocfft_plans.hpp"
 #include "saru.hpp"
-
-#include <rocfft/rocfft.h>
 
 #include <algorithm>
 #include <cmath>
@@ -31,8 +30,6 @@
 #include <vector>
 
 namespace uammd_hip {
-
-int rocfft_setup_once();  // fcm.hip
 
 struct Kern64 {
   int kind;
@@ -293,54 +290,11 @@ struct FCM64 {
   double L[3], viscosity;
   int nxpad = 0;
   size_t planeReal = 0, planeCplx = 0;
-  DeviceBuffer gridBuf, work;
+  DeviceBuffer gridBuf;
   Pse64 pse{0, 0, 0, 0, false};
   bool accumulate = false;
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
-  ~FCM64() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
+  RealFFT fft;
 };
-
-#define UH_ROCFFT64(expr)                                                                      \
-  do {                                                                                         \
-    const rocfft_status s_ = (expr);                                                           \
-    if (s_ != rocfft_status_success) {                                                         \
-      set_last_error("%s failed with rocfft status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-      return -10;                                                                              \
-    }                                                                                          \
-  } while (0)
-
-static int fcm64_plans(FCM64 *f) {
-  rocfft_setup_once();
-  const size_t nx = (size_t)f->grid.cellDim.x, ny = (size_t)f->grid.cellDim.y, nz = (size_t)f->grid.cellDim.z, nkx = nx / 2 + 1;
-  const size_t lengths[3] = {nx, ny, nz};
-  const size_t rstr[3] = {1, (size_t)f->nxpad, (size_t)f->nxpad * ny}, cstr[3] = {1, nkx, nkx * ny};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT64(rocfft_plan_description_create(&d));
-  UH_ROCFFT64(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr, nullptr, 3,
-                                                      rstr, f->planeReal, 3, cstr, f->planeCplx));
-  UH_ROCFFT64(rocfft_plan_create(&f->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_double, 3, lengths, 3, d));
-  UH_ROCFFT64(rocfft_plan_description_destroy(d));
-  UH_ROCFFT64(rocfft_plan_description_create(&d));
-  UH_ROCFFT64(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr, nullptr, 3,
-                                                      cstr, f->planeCplx, 3, rstr, f->planeReal));
-  UH_ROCFFT64(rocfft_plan_create(&f->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_double, 3, lengths, 3, d));
-  UH_ROCFFT64(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT64(rocfft_plan_get_work_buffer_size(f->fwd, &wf));
-  UH_ROCFFT64(rocfft_plan_get_work_buffer_size(f->inv, &wi));
-  const size_t wb = std::max(wf, wi);
-  UH_ROCFFT64(rocfft_execution_info_create(&f->info));
-  if (wb) {
-    if (int e = f->work.reserve(wb)) return e;
-    UH_ROCFFT64(rocfft_execution_info_set_work_buffer(f->info, f->work.ptr, wb));
-  }
-  return 0;
-}
 
 // RPYPSE_near::FandG (pse.hip, host, double)
 void rpy_near_FandG(double r, double rh, double psi, double rcut, double *F, double *G);
@@ -491,44 +445,10 @@ struct BDHI2D64 {
   Kern64 kern{}, kernDriftX{}, kernDriftY{};
   int nxpad = 0;
   size_t planeReal = 0, planeCplx = 0;
-  DeviceBuffer gridBuf, work, drift;   // drift: the thermal drift's constant "quantities" {-T, 0} and {0, -T}
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
+  DeviceBuffer gridBuf, drift;   // drift: the thermal drift's constant "quantities" {-T, 0} and {0, -T}
+  RealFFT fft;
   unsigned int counter = 0;
-  ~BDHI2D64() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
 };
-int next_fft_wise_axis(int n);   // quasi2d.hip
-static int q2d64_plans(BDHI2D64 *q) {
-  if (int e = rocfft_setup_once()) return e;
-  const size_t nx = q->grid.cellDim.x, ny = q->grid.cellDim.y, nkx = nx / 2 + 1;
-  const size_t len[2] = {nx, ny};
-  const size_t rstr[2] = {1, (size_t)q->nxpad}, cstr[2] = {1, nkx};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT64(rocfft_plan_description_create(&d));
-  UH_ROCFFT64(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr, nullptr, 2, rstr,
-                                                      q->planeReal, 2, cstr, q->planeCplx));
-  UH_ROCFFT64(rocfft_plan_create(&q->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_double, 2, len, 2, d));
-  UH_ROCFFT64(rocfft_plan_description_destroy(d));
-  UH_ROCFFT64(rocfft_plan_description_create(&d));
-  UH_ROCFFT64(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr, nullptr, 2, cstr,
-                                                      q->planeCplx, 2, rstr, q->planeReal));
-  UH_ROCFFT64(rocfft_plan_create(&q->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_double, 2, len, 2, d));
-  UH_ROCFFT64(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT64(rocfft_plan_get_work_buffer_size(q->fwd, &wf));
-  UH_ROCFFT64(rocfft_plan_get_work_buffer_size(q->inv, &wi));
-  const size_t w = std::max(wf, wi);
-  UH_ROCFFT64(rocfft_execution_info_create(&q->info));
-  if (w) {
-    if (int e = q->work.reserve(w)) return e;
-    UH_ROCFFT64(rocfft_execution_info_set_work_buffer(q->info, q->work.ptr, w));
-  }
-  return 0;
-}
 
 
 // ---- Poisson with real = double (Interactor/SpectralEwaldPoisson.cu:15-62 closed forms, :71-160 set-up, :222-329 near field, :332-360 and
@@ -678,42 +598,9 @@ struct Poisson64 {
   size_t planeReal = 0, planeCplx = 0;
   double cutoff = 0;
   int ntable = 0;
-  DeviceBuffer tableField, tablePotential, gridQ, planes, gathered, work;
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
-  ~Poisson64() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
+  DeviceBuffer tableField, tablePotential, gridQ, planes, gathered;
+  RealFFT fft;
 };
-static int poisson64_plans(Poisson64 *p) {
-  if (int e = rocfft_setup_once()) return e;
-  const size_t nx = p->cells[0], ny = p->cells[1], nz = p->cells[2], nkx = nx / 2 + 1;
-  const size_t lengths[3] = {nx, ny, nz};
-  const size_t rstr[3] = {1, (size_t)p->nxpad, (size_t)p->nxpad * ny}, cstr[3] = {1, nkx, nkx * ny};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT64(rocfft_plan_description_create(&d));
-  UH_ROCFFT64(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr, nullptr, 3, rstr,
-                                                      p->planeReal, 3, cstr, p->planeCplx));
-  UH_ROCFFT64(rocfft_plan_create(&p->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_double, 3, lengths, 1, d));
-  UH_ROCFFT64(rocfft_plan_description_destroy(d));
-  UH_ROCFFT64(rocfft_plan_description_create(&d));
-  UH_ROCFFT64(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr, nullptr, 3, cstr,
-                                                      p->planeCplx, 3, rstr, p->planeReal));
-  UH_ROCFFT64(rocfft_plan_create(&p->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_double, 3, lengths, 4, d));
-  UH_ROCFFT64(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT64(rocfft_plan_get_work_buffer_size(p->fwd, &wf));
-  UH_ROCFFT64(rocfft_plan_get_work_buffer_size(p->inv, &wi));
-  const size_t w = std::max(wf, wi);
-  UH_ROCFFT64(rocfft_execution_info_create(&p->info));
-  if (w) {
-    if (int e = p->work.reserve(w)) return e;
-    UH_ROCFFT64(rocfft_execution_info_set_work_buffer(p->info, p->work.ptr, w));
-  }
-  return 0;
-}
 static Table64 view64(const DeviceBuffer &b, int ntable, double rmax) {
   return Table64{(const double *)b.ptr, ntable - 1, rmax, 1.0 / rmax, 1.0 / (double)(ntable - 1)};
 }
@@ -726,15 +613,13 @@ static int poisson64_far(Poisson64 *p, const double *d_pos, const double *d_char
   UH_CHECK(hipMemsetAsync(gq, 0, sizeof(double) * p->planeReal, st));
   hipLaunchKernelGGL((k_ibm64<1, true>), gp, bp, 0, st, d_pos, 4, d_charge, 1, (double *)nullptr, gq, N, p->grid, p->nxpad, (size_t)1, (size_t)1, p->kern,
                      dsx, dsxy, false, false);
-  UH_ROCFFT64(rocfft_execution_info_set_stream(p->info, (void *)st));
-  void *bq[1] = {gq};
-  UH_ROCFFT64(rocfft_execute(p->fwd, bq, nullptr, p->info));
+  if (int e = p->fft.set_stream((void *)st)) return e;
+  if (int e = p->fft.forward(gq)) return e;
   const int3 n = p->grid.cellDim;
   const size_t total = p->planeCplx;
   hipLaunchKernelGGL(k_poisson_convolve64, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double2 *)gq, (double2 *)p->planes.ptr,
                      p->planeCplx, n, real3d{p->L[0], p->L[1], p->L[2]}, p->par.epsilon);
-  void *bpl[1] = {p->planes.ptr};
-  UH_ROCFFT64(rocfft_execute(p->inv, bpl, nullptr, p->info));
+  if (int e = p->fft.inverse(p->planes.ptr)) return e;
   if (int e = p->gathered.reserve(sizeof(double) * 4 * (size_t)N)) return e;
   hipLaunchKernelGGL((k_ibm64<4, false>), gp, bp, 0, st, d_pos, 4, (const double *)nullptr, 4, (double *)p->gathered.ptr, (double *)p->planes.ptr, N, p->grid,
                      p->nxpad, (size_t)1, p->planeReal, p->kern, dsx, dsxy, false, true);
@@ -749,7 +634,6 @@ template <int MODE> static int poisson64_near(Poisson64 *p, const double *d_pos,
   UH_CHECK(hipGetLastError());
   return 0;
 }
-int next_fft_wise_axis(int n);   // quasi2d.hip
 
 static double fcm_upsampling64(double tolerance) {  // FCM_kernels.cuh:24-30
   const double amin = 0.55, amax = 1.65;
@@ -851,11 +735,9 @@ int uammd_fcm_create_f64(const uammd_fcm_parameters_f64 *par, uammd_fcm_f64 **ou
   f->kern = to_dev64(par->kernel);
   for (int a = 0; a < 3; ++a) f->L[a] = par->boxSize[a];
   f->viscosity = par->viscosity;
-  f->nxpad = 2 * (par->cells[0] / 2 + 1);
-  f->planeReal = (size_t)f->nxpad * par->cells[1] * par->cells[2];
-  f->planeCplx = f->planeReal / 2;
+  fft_padded_layout(3, par->cells, &f->nxpad, &f->planeReal, &f->planeCplx);
   if (int e = f->gridBuf.reserve(sizeof(double) * 3 * f->planeReal)) { delete f; return e; }
-  if (int e = fcm64_plans(f)) { delete f; return e; }
+  if (int e = f->fft.create(3, par->cells, f->nxpad, f->planeReal, f->planeCplx, rocfft_precision_double, 3, 3)) { delete f; return e; }
   *out = reinterpret_cast<uammd_fcm_f64 *>(f);
   return 0;
 }
@@ -881,13 +763,12 @@ int uammd_fcm_displacements_thermal_f64(uammd_fcm_f64 *h, const double *d_pos, c
     if (!f->accumulate) UH_CHECK(hipMemsetAsync(d_velocity, 0, sizeof(double) * 3 * (size_t)N, st));
     return 0;
   }
-  UH_ROCFFT64(rocfft_execution_info_set_stream(f->info, st));
-  void *bufs[1] = {g};
+  if (int e = f->fft.set_stream((void *)st)) return e;
   if (d_force) {
     UH_CHECK(hipMemsetAsync(g, 0, sizeof(double) * 3 * f->planeReal, st));
     hipLaunchKernelGGL((k_ibm64<3, true>), gp, bp, 0, st, d_pos, 4, d_force, 4, (double *)nullptr, g, N, f->grid, f->nxpad, (size_t)1, f->planeReal,
                        f->kern, dsx, dsxy, false, false);
-    UH_ROCFFT64(rocfft_execute(f->fwd, bufs, nullptr, f->info));
+    if (int e = f->fft.forward(g)) return e;
   }
   double noisePrefactor = 0.0;
   if (thermal) {
@@ -899,7 +780,7 @@ int uammd_fcm_displacements_thermal_f64(uammd_fcm_f64 *h, const double *d_pos, c
   const size_t total = f->planeCplx;
   hipLaunchKernelGGL(k_kspace64, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (double2 *)g, f->planeCplx, f->grid.cellDim,
                      real3d{f->L[0], f->L[1], f->L[2]}, f->viscosity, f->pse, d_force != nullptr, noisePrefactor, seed1, seed2);
-  UH_ROCFFT64(rocfft_execute(f->inv, bufs, nullptr, f->info));
+  if (int e = f->fft.inverse(g)) return e;
   hipLaunchKernelGGL((k_ibm64<3, false>), gp, bp, 0, st, d_pos, 4, (const double *)nullptr, 3, d_velocity, g, N, f->grid, f->nxpad, (size_t)1,
                      f->planeReal, f->kern, dsx, dsxy, false, !f->accumulate);
   UH_CHECK(hipGetLastError());
@@ -1186,8 +1067,8 @@ int uammd_bdhi2d_create_f64(const uammd_bdhi2d_parameters_f64 *par, uammd_bdhi2d
   int cd[2] = {par->cells[0], par->cells[1]};
   if (cd[0] <= 0) {  // initializeGrid, .cu:61-73
     const double h = a * 0.8;
-    cd[0] = next_fft_wise_axis((int)(par->boxSize[0] / h));
-    cd[1] = next_fft_wise_axis((int)(par->boxSize[1] / h));
+    cd[0] = next_fft_wise((int)(par->boxSize[0] / h));
+    cd[1] = next_fft_wise((int)(par->boxSize[1] / h));
   }
   const double L3[3] = {par->boxSize[0], par->boxSize[1], 0.0};
   const int per[3] = {1, 1, 0};
@@ -1206,16 +1087,14 @@ int uammd_bdhi2d_create_f64(const uammd_bdhi2d_parameters_f64 *par, uammd_bdhi2d
   q->kernDriftX.prefactor = -std::sqrt(1.0 / (2.0 * M_PI * w * w));
   q->kernDriftY = q->kernDriftX;
   q->kernDriftY.kind = kKernelGauss2DDriftY;
-  q->nxpad = 2 * (cd[0] / 2 + 1);
-  q->planeReal = (size_t)q->nxpad * cd[1];
-  q->planeCplx = (size_t)(cd[0] / 2 + 1) * cd[1];
+  fft_padded_layout(2, cd, &q->nxpad, &q->planeReal, &q->planeCplx);
   int e = q->gridBuf.reserve(sizeof(double) * 2 * q->planeReal);
   if (!e) e = q->drift.reserve(sizeof(double) * 4);
   if (!e) {
     const double T = par->temperature, c[4] = {-T, 0.0, 0.0, -T};
     if (hipMemcpy(q->drift.ptr, c, sizeof(c), hipMemcpyHostToDevice) != hipSuccess) { set_last_error("uammd_bdhi2d_create_f64: hipMemcpy failed"); e = -4; }
   }
-  if (!e) e = q2d64_plans(q);
+  if (!e) e = q->fft.create(2, cd, q->nxpad, q->planeReal, q->planeCplx, rocfft_precision_double, 2, 2);
   if (e) { delete q; return e; }
   if (cells) { cells[0] = cd[0]; cells[1] = cd[1]; }
   if (support) *support = s;
@@ -1239,8 +1118,7 @@ int uammd_bdhi2d_velocities_f64(uammd_bdhi2d_f64 *h, const double *d_pos, const 
   const dim3 gp((N + 3) / 4), bp(256);
   const FastDiv dsx = make_fastdiv(q->kern.support.x), dsxy = make_fastdiv(q->kern.support.x * q->kern.support.y);
   const int nx = q->grid.cellDim.x, ny = q->grid.cellDim.y;
-  UH_ROCFFT64(rocfft_execution_info_set_stream(q->info, (void *)st));
-  void *bufs[1] = {g};
+  if (int e = q->fft.set_stream((void *)st)) return e;
   const double *c = (const double *)q->drift.ptr;
 #define UH_Q2D_SPREAD(quantity, qstride, kernel)                                                                                                 \
   hipLaunchKernelGGL((k_ibm64<2, true>), gp, bp, 0, st, d_pos, 4, quantity, qstride, (double *)nullptr, g, N, q->grid, q->nxpad, (size_t)1, q->planeReal, \
@@ -1252,7 +1130,7 @@ int uammd_bdhi2d_velocities_f64(uammd_bdhi2d_f64 *h, const double *d_pos, const 
       UH_Q2D_SPREAD(c + 2, 0, q->kernDriftY);
     }
     if (d_force) UH_Q2D_SPREAD(d_force, 4, q->kern);   // spreadParticleForces, .cu:268-283
-    UH_ROCFFT64(rocfft_execute(q->fwd, bufs, nullptr, q->info));
+    if (int e = q->fft.forward(g)) return e;
   }
 #undef UH_Q2D_SPREAD
   if (!deterministic && !(T > 0)) {  // nothing moves the particles
@@ -1268,7 +1146,7 @@ int uammd_bdhi2d_velocities_f64(uammd_bdhi2d_f64 *h, const double *d_pos, const 
   hipLaunchKernelGGL(k_q2d_kspace64, dim3((total + 255) / 256), dim3(256), 0, st, (double2 *)g, (double2 *)g + q->planeCplx, nx, ny, q->par.boxSize[0],
                      q->par.boxSize[1], q->par.kernel, q->par.hydrodynamicRadius, q->par.viscosity, deterministic, noisePrefactor, q->par.seed,
                      q->counter);
-  UH_ROCFFT64(rocfft_execute(q->inv, bufs, nullptr, q->info));
+  if (int e = q->fft.inverse(g)) return e;
   hipLaunchKernelGGL((k_ibm64<2, false>), gp, bp, 0, st, d_pos, 4, (const double *)nullptr, 2, d_vel, g, N, q->grid, q->nxpad, (size_t)1, q->planeReal,
                      q->kern, dsx, dsxy, true, true);
   UH_CHECK(hipGetLastError());
@@ -1300,7 +1178,7 @@ int uammd_poisson_create_f64(const uammd_poisson_parameters_f64 *par, uammd_pois
   if (par->upsampling > 0) h = 1.0 / par->upsampling;
   else h = (1.3 - std::min((-std::log10(tolerance)) / 10.0, 0.9)) * fw;
   h = std::min(h, p->L[0] / 32.0);
-  for (int a = 0; a < 3; ++a) p->cells[a] = next_fft_wise_axis((int)(p->L[a] / h));
+  for (int a = 0; a < 3; ++a) p->cells[a] = next_fft_wise((int)(p->L[a] / h));
   const int per[3] = {1, 1, 1};
   p->grid = make_grid<double>(make_box<double>(p->L, per), make_int3(p->cells[0], p->cells[1], p->cells[2]));
   const double hx = p->grid.cellSize.x;
@@ -1359,12 +1237,10 @@ int uammd_poisson_create_f64(const uammd_poisson_parameters_f64 *par, uammd_pois
       return -4;
     }
   }
-  p->nxpad = 2 * (p->cells[0] / 2 + 1);
-  p->planeReal = (size_t)p->nxpad * p->cells[1] * p->cells[2];
-  p->planeCplx = (size_t)(p->cells[0] / 2 + 1) * p->cells[1] * p->cells[2];
+  fft_padded_layout(3, p->cells, &p->nxpad, &p->planeReal, &p->planeCplx);
   int e = p->gridQ.reserve(sizeof(double) * p->planeReal);
   if (!e) e = p->planes.reserve(sizeof(double) * 4 * p->planeReal);
-  if (!e) e = poisson64_plans(p);
+  if (!e) e = p->fft.create(3, p->cells, p->nxpad, p->planeReal, p->planeCplx, rocfft_precision_double, 1, 4);
   if (e) { delete p; return e; }
   if (info) {
     for (int a = 0; a < 3; ++a) info->cells[a] = p->cells[a];

@@ -18,24 +18,13 @@
 //   * all work buffers are owned by the handle; steady state allocates nothing.
 #include "ibm.hpp"
 #include "celllist.hpp"
+#include "rocfft_plans.hpp"
 #include "saru.hpp"
 
-#include <rocfft/rocfft.h>
-
 #include <cmath>
-#include <mutex>
 #include <string>
 
 namespace uammd_hip {
-
-#define UH_ROCFFT(expr)                                                                      \
-  do {                                                                                       \
-    rocfft_status s_ = (expr);                                                               \
-    if (s_ != rocfft_status_success) {                                                       \
-      set_last_error("%s failed with rocfft_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-      return -10 - (int)s_;                                                                  \
-    }                                                                                        \
-  } while (0)
 
 // PSE far field (FarField.cuh:85-119): hydrodynamic radius, Ewald splitting, kernel splitting, shear strain
 struct PseGreens { float rh, split, eta, shear; bool on; };
@@ -75,7 +64,7 @@ struct FCM {
   int nxpad = 0;           // 2*(nx/2+1)
   size_t planeReal = 0;    // floats per component plane
   size_t planeCplx = 0;    // complex per component plane
-  DeviceBuffer gridBuf, gridBufT, interBuf, work, prepOrigin, prepWeights, prepTileOf, prepRank, prepTileCount, prepTileStart, prepSorted;
+  DeviceBuffer gridBuf, gridBufT, interBuf, prepOrigin, prepWeights, prepTileOf, prepRank, prepTileCount, prepTileStart, prepSorted;
   int emVelN = 0;
   DeviceBuffer emVel;              // velocities of uammd_fcm_step_euler_maruyama when the caller keeps none
   bool emBin = true;               // uammd_fcm_step_euler_maruyama: the update kernel also bins the positions it writes for the next call
@@ -113,26 +102,15 @@ struct FCM {
   int zTileLog2 = 0;               // test / tuning hook: log2 of the fused z pass's node tile (0 = default)
   bool customFFT = true;           // power-of-two grids: the five-pass LDS FFT pipeline of fcm_fft.hpp instead of rocFFT + k_fcm_kspace
   PseGreens pse{0.f, 0.f, 0.f, 0.f, false};  // PSE far field: Hasimoto-split RPY greens function instead of 1/(eta k^2)
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
-  size_t workBytes = 0;
+  RealFFT fft;             // (the z-slab solver runs its own four plans through this one's info and work buffer)
   unsigned int seed2 = 0;  // the reference's `static uint seed2` (FCM_impl.cuh:517): per-handle here
   FcmPrep halfPrep{};      // a solve queued in two halves (fcm_displacements_impl): the stencil view of the first for the second
   int halfN = 0;
   bool halfPending = false;
   ~FCM() {
     if (slotFlagHost) (void)hipHostFree(slotFlagHost);
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
   }
 };
-
-static std::once_flag g_rocfft_once;
-int rocfft_setup_once() {  // shared with poisson.hip
-  std::call_once(g_rocfft_once, []() { (void)rocfft_setup(); });
-  return 0;
-}
 
 // ---- spread / gather on the planar grids ---------------------------------------------------------------
 template <bool SPREAD>
@@ -1847,38 +1825,6 @@ static int fcm_fft_inverse_x(FCM *f, float *g, float4 *inter, hipStream_t st, bo
   return 0;
 }
 
-static int fcm_make_plans(FCM *f) {
-  std::call_once(g_rocfft_once, []() { (void)rocfft_setup(); });
-  const size_t nx = (size_t)f->grid.cellDim.x, ny = (size_t)f->grid.cellDim.y, nz = (size_t)f->grid.cellDim.z;
-  const size_t nkx = nx / 2 + 1;
-  const size_t lengths[3] = {nx, ny, nz};
-  const size_t rstr[3] = {1, (size_t)f->nxpad, (size_t)f->nxpad * ny};
-  const size_t cstr[3] = {1, nkx, nkx * ny};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved,
-                                                     nullptr, nullptr, 3, rstr, f->planeReal, 3, cstr, f->planeCplx));
-  UH_ROCFFT(rocfft_plan_create(&f->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward,
-                               rocfft_precision_single, 3, lengths, 3, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
-                                                     nullptr, nullptr, 3, cstr, f->planeCplx, 3, rstr, f->planeReal));
-  UH_ROCFFT(rocfft_plan_create(&f->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse,
-                               rocfft_precision_single, 3, lengths, 3, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(f->fwd, &wf));
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(f->inv, &wi));
-  f->workBytes = wf > wi ? wf : wi;
-  if (f->workBytes) {
-    if (int e = f->work.reserve(f->workBytes)) return e;
-  }
-  UH_ROCFFT(rocfft_execution_info_create(&f->info));
-  if (f->workBytes) UH_ROCFFT(rocfft_execution_info_set_work_buffer(f->info, f->work.ptr, f->workBytes));
-  return 0;
-}
-
 // bins the particles by tile and fills the tile-sorted stencil origins / weights / forces (reused by spread and gather)
 static int fcm_prepare_tiles(FCM *f, const float *d_pos, const float *d_force, int N, hipStream_t st, FcmPrep *out, bool positionsKept = false) {
   const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
@@ -1990,50 +1936,20 @@ static bool fcm_slab_custom_fft(const FCMSlab *s) {
   return s->loc.customFFT && s->cells.x % 2 == 0 && fft_axis_ok(s->cells.x, 16, 512) && fft_axis_ok(s->cells.y, 2, 256);
 }
 static int fcm_slab_make_plans(FCMSlab *s) {
-  std::call_once(g_rocfft_once, []() { (void)rocfft_setup(); });
   FCM *f = &s->loc;
   const size_t nx = (size_t)s->cells.x, ny = (size_t)s->cells.y, nz = (size_t)s->cells.z, nkx = (size_t)s->nkx;
   const size_t len2[2] = {nx, ny};
   const size_t rstr[2] = {1, (size_t)f->nxpad}, cstr[2] = {1, nkx};
   const size_t rdist = (size_t)f->nxpad * ny, cdist = nkx * ny, batchXY = 3 * (size_t)s->nzl;
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved,
-                                                     nullptr, nullptr, 2, rstr, rdist, 2, cstr, cdist));
-  UH_ROCFFT(rocfft_plan_create(&s->fwdXY, rocfft_placement_inplace, rocfft_transform_type_real_forward,
-                               rocfft_precision_single, 2, len2, batchXY, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
-                                                     nullptr, nullptr, 2, cstr, cdist, 2, rstr, rdist));
-  UH_ROCFFT(rocfft_plan_create(&s->invXY, rocfft_placement_inplace, rocfft_transform_type_real_inverse,
-                               rocfft_precision_single, 2, len2, batchXY, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
+  if (int e = rocfft_make_plan(&s->fwdXY, rocfft_transform_type_real_forward, rocfft_precision_single, 2, len2, rstr, rdist, cstr, cdist, batchXY))
+    return e;
+  if (int e = rocfft_make_plan(&s->invXY, rocfft_transform_type_real_inverse, rocfft_precision_single, 2, len2, cstr, cdist, rstr, rdist, batchXY))
+    return e;
   const size_t S = 3 * (size_t)s->nyl * nkx;
   const size_t len1[1] = {nz}, zstr[1] = {S};
-  for (int inverse = 0; inverse < 2; ++inverse) {
-    UH_ROCFFT(rocfft_plan_description_create(&d));
-    UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_complex_interleaved,
-                                                       rocfft_array_type_complex_interleaved, nullptr, nullptr, 1, zstr, 1, 1,
-                                                       zstr, 1));
-    UH_ROCFFT(rocfft_plan_create(inverse ? &s->invZ : &s->fwdZ, rocfft_placement_inplace,
-                                 inverse ? rocfft_transform_type_complex_inverse : rocfft_transform_type_complex_forward,
-                                 rocfft_precision_single, 1, len1, S, d));
-    UH_ROCFFT(rocfft_plan_description_destroy(d));
-  }
-  size_t w = 0;
-  for (rocfft_plan p : {s->fwdXY, s->invXY, s->fwdZ, s->invZ}) {
-    size_t wi = 0;
-    UH_ROCFFT(rocfft_plan_get_work_buffer_size(p, &wi));
-    w = wi > w ? wi : w;
-  }
-  f->workBytes = w;
-  if (w) {
-    if (int e = f->work.reserve(w)) return e;
-  }
-  UH_ROCFFT(rocfft_execution_info_create(&f->info));
-  if (w) UH_ROCFFT(rocfft_execution_info_set_work_buffer(f->info, f->work.ptr, w));
-  return 0;
+  if (int e = rocfft_make_plan(&s->fwdZ, rocfft_transform_type_complex_forward, rocfft_precision_single, 1, len1, zstr, 1, zstr, 1, S)) return e;
+  if (int e = rocfft_make_plan(&s->invZ, rocfft_transform_type_complex_inverse, rocfft_precision_single, 1, len1, zstr, 1, zstr, 1, S)) return e;
+  return f->fft.create_info({s->fwdXY, s->invXY, s->fwdZ, s->invZ});
 }
 
 }  // namespace uammd_hip
@@ -2079,13 +1995,11 @@ int uammd_fcm_create(const uammd_fcm_parameters *par, uammd_fcm **out) {
   const BoxT<float> box = make_box<float>(par->boxSize, periodic);
   f->grid = make_grid<float>(box, make_int3(par->cells[0], par->cells[1], par->cells[2]));
   f->kern = to_dev(par->kernel);
-  f->nxpad = 2 * (par->cells[0] / 2 + 1);
-  f->planeReal = (size_t)f->nxpad * par->cells[1] * par->cells[2];
-  f->planeCplx = f->planeReal / 2;
+  fft_padded_layout(3, par->cells, &f->nxpad, &f->planeReal, &f->planeCplx);
   if (int e = f->gridBuf.reserve(sizeof(float) * 3 * f->planeReal)) { delete f; return e; }
   f->useTiles = fcm_tiles_usable(par->cells, par->kernel.support, &f->tdim);
   f->ntiles = make_int3(par->cells[0] / f->tdim.x, par->cells[1] / f->tdim.y, par->cells[2] / f->tdim.z);
-  if (int e = fcm_make_plans(f)) { delete f; return e; }
+  if (int e = f->fft.create(3, par->cells, f->nxpad, f->planeReal, f->planeCplx, rocfft_precision_single, 3, 3)) { delete f; return e; }
   *out = reinterpret_cast<uammd_fcm *>(f);
   return 0;
 }
@@ -2180,8 +2094,7 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
   float *g = (float *)f->gridBuf.ptr;
   const dim3 gp((N + 3) / 4), bp(256);
   const FastDiv dsx = make_fastdiv(f->kern.support.x), dsxy = make_fastdiv(f->kern.support.x * f->kern.support.y);
-  UH_ROCFFT(rocfft_execution_info_set_stream(f->info, (void *)st));
-  void *bufs[1] = {g};
+  if (int e = f->fft.set_stream((void *)st)) return e;
   const size_t zs = (size_t)f->nxpad * f->grid.cellDim.y;  // planar component grids: z stride = one xy plane
   const bool tiles = f->useTiles && !f->forceAtomicSpread;
   const bool custom = stage == 0 && fcm_custom_fft_usable(f);  // (stage 1 exports the Fourier grid, which the fused z pass never stores)
@@ -2234,7 +2147,7 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
                          (float *)nullptr, g, N, f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, false);
     }
     if (custom) { if (int e = fcm_fft_forward_xy(f, g, st)) return e; }
-    else UH_ROCFFT(rocfft_execute(f->fwd, bufs, nullptr, f->info));
+    else if (int e = f->fft.forward(g)) return e;
   }
   if (half == 1) {
     f->halfPrep = pr;
@@ -2262,7 +2175,7 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
                        f->grid.cellDim, real3f{f->par.boxSize[0], f->par.boxSize[1], f->par.boxSize[2]}, f->par.viscosity,
                        d_force != nullptr, noisePrefactor, f->par.seed, f->seed2, f->pse);
     if (stage == 1) { UH_CHECK(hipGetLastError()); return 0; }
-    UH_ROCFFT(rocfft_execute(f->inv, bufs, nullptr, f->info));
+    if (int e = f->fft.inverse(g)) return e;
   }
   const bool interPath = tiles && f->interGather && !(tiles && (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6) && f->tileGather);
   if (custom && !interPath) { if (int e = fcm_fft_inverse_x(f, g, nullptr, st)) return e; }
@@ -2666,10 +2579,8 @@ int uammd_fcm_slab_forward_xy(uammd_fcm_slab *h, float *d_grid, void *stream) {
     UH_CHECK(hipGetLastError());
     return 0;
   }
-  UH_ROCFFT(rocfft_execution_info_set_stream(s->loc.info, stream));
-  void *io[1] = {(void *)owned};
-  UH_ROCFFT(rocfft_execute(s->fwdXY, io, nullptr, s->loc.info));
-  return 0;
+  if (int e = s->loc.fft.set_stream(stream)) return e;
+  return s->loc.fft.execute(s->fwdXY, owned);
 }
 
 // batched 2-D C2R of the owned part of the window, in place; the halo planes are left untouched
@@ -2693,10 +2604,8 @@ int uammd_fcm_slab_inverse_xy(uammd_fcm_slab *h, float *d_grid, void *stream) {
     UH_CHECK(hipGetLastError());
     return 0;
   }
-  UH_ROCFFT(rocfft_execution_info_set_stream(s->loc.info, stream));
-  void *io[1] = {(void *)owned};
-  UH_ROCFFT(rocfft_execute(s->invXY, io, nullptr, s->loc.info));
-  return 0;
+  if (int e = s->loc.fft.set_stream(stream)) return e;
+  return s->loc.fft.execute(s->invXY, owned);
 }
 
 // The same inverse writing the OWNED planes of the gather's float4 window d_inter [z][y][x] = (vx, vy, vz, 0) (nz window planes of
@@ -2758,10 +2667,8 @@ int uammd_fcm_slab_gather_inter(uammd_fcm_slab *h, const float *d_posLocal, int 
 int uammd_fcm_slab_fft_z(uammd_fcm_slab *h, float *d_cplxZ, int inverse, void *stream) {
   if (!h || !d_cplxZ) { set_last_error("uammd_fcm_slab_fft_z: null argument"); return -1; }
   FCMSlab *s = reinterpret_cast<FCMSlab *>(h);
-  UH_ROCFFT(rocfft_execution_info_set_stream(s->loc.info, stream));
-  void *io[1] = {d_cplxZ};
-  UH_ROCFFT(rocfft_execute(inverse ? s->invZ : s->fwdZ, io, nullptr, s->loc.info));
-  return 0;
+  if (int e = s->loc.fft.set_stream(stream)) return e;
+  return s->loc.fft.execute(inverse ? s->invZ : s->fwdZ, d_cplxZ);
 }
 
 // z transform + Fourier-space operator + inverse z transform of d_cplxZ [z][c][yl][kx] in one pass (power-of-two nz; returns 1 when
@@ -2941,8 +2848,7 @@ int uammd_fcm_displacements_torque(uammd_fcm *h, const float *d_pos, const float
   float *g = (float *)f->gridBuf.ptr, *gT = (float *)f->gridBufT.ptr;
   const size_t zs = (size_t)f->nxpad * f->grid.cellDim.y;
   const dim3 gp((N + 3) / 4), bp(256);
-  UH_ROCFFT(rocfft_execution_info_set_stream(f->info, (void *)st));
-  void *bufs[1] = {g}, *bufsT[1] = {gT};
+  if (int e = f->fft.set_stream((void *)st)) return e;
   const int total = (int)f->planeCplx;
   const dim3 gk((total + 255) / 256);
   const real3f L{f->par.boxSize[0], f->par.boxSize[1], f->par.boxSize[2]};
@@ -2954,7 +2860,7 @@ int uammd_fcm_displacements_torque(uammd_fcm *h, const float *d_pos, const float
     if (d_force) {
       hipLaunchKernelGGL((k_fcm_ibm<true>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)d_force, (float *)nullptr, g, N,
                          f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, false);
-      UH_ROCFFT(rocfft_execute(f->fwd, bufs, nullptr, f->info));
+      if (int e = f->fft.forward(g)) return e;
     }
   }
   // torques: spread with the torque window, transform, add half the curl to the Fourier forces
@@ -2962,7 +2868,7 @@ int uammd_fcm_displacements_torque(uammd_fcm *h, const float *d_pos, const float
   UH_CHECK(hipMemsetAsync(gT, 0, sizeof(float) * 3 * f->planeReal, st));
   hipLaunchKernelGGL((k_fcm_ibm<true>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)d_torque, (float *)nullptr, gT, N,
                      f->grid, f->nxpad, f->planeReal, zs, f->kernT, tsx, tsxy, false);
-  UH_ROCFFT(rocfft_execute(f->fwd, bufsT, nullptr, f->info));
+  if (int e = f->fft.forward(gT)) return e;
   hipLaunchKernelGGL((k_fcm_half_curl<true>), gk, bp, 0, st, (const float2 *)gT, (float2 *)g, f->planeCplx, f->grid.cellDim, L, dNkx, dNy);
   // Stokes + noise (the grid holds Fourier forces even when d_force is NULL: it was zeroed above)
   float noisePrefactor = 0.0f;
@@ -2976,10 +2882,10 @@ int uammd_fcm_displacements_torque(uammd_fcm *h, const float *d_pos, const float
                      f->par.seed, f->seed2, f->pse);
   // angular velocity = half the curl of the velocity, interpolated with the torque window
   hipLaunchKernelGGL((k_fcm_half_curl<false>), gk, bp, 0, st, (const float2 *)g, (float2 *)gT, f->planeCplx, f->grid.cellDim, L, dNkx, dNy);
-  UH_ROCFFT(rocfft_execute(f->inv, bufsT, nullptr, f->info));
+  if (int e = f->fft.inverse(gT)) return e;
   hipLaunchKernelGGL((k_fcm_ibm<false>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)nullptr, d_angularVelocity, gT, N,
                      f->grid, f->nxpad, f->planeReal, zs, f->kernT, tsx, tsxy, false);
-  UH_ROCFFT(rocfft_execute(f->inv, bufs, nullptr, f->info));
+  if (int e = f->fft.inverse(g)) return e;
   {
     const FastDiv dsx = make_fastdiv(f->kern.support.x), dsxy = make_fastdiv(f->kern.support.x * f->kern.support.y);
     hipLaunchKernelGGL((k_fcm_ibm<false>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)nullptr, d_linearVelocity, g, N,

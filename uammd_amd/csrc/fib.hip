@@ -13,25 +13,13 @@
 // The reference draws the 6 N_cells fluid random numbers with cuRAND (third party, stream unpinned); here they come from
 // Saru(cell + slot * N_cells, seed, step), or from the caller (uammd_fib_set_noise) for the parity tests.
 #include "celllist.hpp"
+#include "rocfft_plans.hpp"
 #include "stagger.hpp"
-
-#include <rocfft/rocfft.h>
 
 #include <algorithm>
 #include <cmath>
 
 namespace uammd_hip {
-
-int rocfft_setup_once();  // fcm.hip
-
-#define UH_ROCFFT(expr)                                                                      \
-  do {                                                                                       \
-    rocfft_status s_ = (expr);                                                               \
-    if (s_ != rocfft_status_success) {                                                       \
-      set_last_error("%s failed with rocfft_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-      return -10 - (int)s_;                                                                  \
-    }                                                                                        \
-  } while (0)
 
 struct FIB {
   uammd_fib_parameters par{};
@@ -39,62 +27,11 @@ struct FIB {
   float hKernel = 0.f, rh = 0.f;
   int nxpad = 0;
   size_t planeReal = 0, planeCplx = 0;
-  DeviceBuffer gridBuf, random, posOld, work;
+  DeviceBuffer gridBuf, random, posOld;
   const float *externalNoise = nullptr;
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
+  RealFFT fft;
   unsigned long long step = 0;
-  ~FIB() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
 };
-
-static int next_fft_wise3(int n) {  // FIB_ns::nextFFTWiseSize3D (FIB.cu:31-84) = utils/Grid.cuh:142-213, one axis
-  static const int primes[5] = {2, 3, 5, 7, 11}, maxExp[5] = {64, 64, 5, 4, 3};
-  for (int c = std::max(n, 1);; ++c) {
-    if (c % 2) continue;
-    int m = c;
-    bool ok = true;
-    for (int p = 0; p < 5; ++p) {
-      int e = 0;
-      while (m % primes[p] == 0) { m /= primes[p]; ++e; }
-      ok = ok && e <= maxExp[p];
-    }
-    if (ok && m == 1) return c;
-  }
-}
-
-static int fib_make_plans(FIB *f) {
-  if (int e = rocfft_setup_once()) return e;
-  const size_t nx = f->grid.cellDim.x, ny = f->grid.cellDim.y, nz = f->grid.cellDim.z, nkx = nx / 2 + 1;
-  const size_t lengths[3] = {nx, ny, nz};
-  const size_t rstr[3] = {1, (size_t)f->nxpad, (size_t)f->nxpad * ny}, cstr[3] = {1, nkx, nkx * ny};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr, nullptr,
-                                                     3, rstr, f->planeReal, 3, cstr, f->planeCplx));
-  UH_ROCFFT(rocfft_plan_create(&f->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_single, 3, lengths,
-                               3, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr, nullptr,
-                                                     3, cstr, f->planeCplx, 3, rstr, f->planeReal));
-  UH_ROCFFT(rocfft_plan_create(&f->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_single, 3, lengths,
-                               3, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(f->fwd, &wf));
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(f->inv, &wi));
-  const size_t w = std::max(wf, wi);
-  UH_ROCFFT(rocfft_execution_info_create(&f->info));
-  if (w) {
-    if (int e = f->work.reserve(w)) return e;
-    UH_ROCFFT(rocfft_execution_info_set_work_buffer(f->info, f->work.ptr, w));
-  }
-  return 0;
-}
 
 }  // namespace uammd_hip
 
@@ -122,7 +59,7 @@ int uammd_fib_create(const uammd_fib_parameters *par, uammd_fib **out, int cells
   int cd[3] = {par->cells[0], par->cells[1], par->cells[2]};
   if (cd[0] < 0) {
     const float hgrid = par->hydrodynamicRadius / 0.91f;  // Peskin::threePoint::adviseGridSize, FIB_kernels.cuh:118-120
-    for (int a = 0; a < 3; ++a) cd[a] = next_fft_wise3((int)(par->boxSize[a] / hgrid));
+    for (int a = 0; a < 3; ++a) cd[a] = next_fft_wise((int)(par->boxSize[a] / hgrid));
   }
   if (cd[0] < 3) cd[0] = 3;
   if (cd[1] < 3) cd[1] = 3;
@@ -136,12 +73,10 @@ int uammd_fib_create(const uammd_fib_parameters *par, uammd_fib **out, int cells
   f->grid = make_grid(make_box<float>(par->boxSize, per), make_int3(cd[0], cd[1], cd[2]));
   f->hKernel = std::min(f->grid.cellSize.x, std::min(f->grid.cellSize.y, f->grid.cellSize.z));
   f->rh = f->grid.cellSize.x * 0.91f;  // fixHydrodynamicRadius(h, cellSize.x), FIB.cu:121
-  f->nxpad = 2 * (cd[0] / 2 + 1);
-  f->planeReal = (size_t)f->nxpad * cd[1] * cd[2];
-  f->planeCplx = (size_t)(cd[0] / 2 + 1) * cd[1] * cd[2];
+  fft_padded_layout(3, cd, &f->nxpad, &f->planeReal, &f->planeCplx);
   int e = f->gridBuf.reserve(sizeof(float) * 3 * f->planeReal);
   if (!e && par->temperature != 0.0f) e = f->random.reserve(sizeof(float) * 6 * (size_t)cd[0] * cd[1] * cd[2]);
-  if (!e) e = fib_make_plans(f);
+  if (!e) e = f->fft.create(3, cd, f->nxpad, f->planeReal, f->planeCplx, rocfft_precision_single, 3, 3);
   if (e) { delete f; return e; }
   if (cells) for (int a = 0; a < 3; ++a) cells[a] = cd[a];
   if (hydrodynamicRadius) *hydrodynamicRadius = f->rh;
@@ -189,14 +124,13 @@ int uammd_fib_forward(uammd_fib *h, float *d_pos, const float *d_force, int N, v
   if (d_force)
     hipLaunchKernelGGL(k_fib_spread, gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)d_force, g, f->planeReal, f->nxpad, N, f->grid, invh,
                        1.0f);
-  UH_ROCFFT(rocfft_execution_info_set_stream(f->info, (void *)st));
-  void *bufs[1] = {g};
-  UH_ROCFFT(rocfft_execute(f->fwd, bufs, nullptr, f->info));
+  if (int e = f->fft.set_stream((void *)st)) return e;
+  if (int e = f->fft.forward(g)) return e;
   const uint total = (uint)f->planeCplx;
   hipLaunchKernelGGL((k_fib_stokes<false>), dim3((total + 255) / 256), dim3(256), 0, st, (float2 *)g, f->planeCplx, n,
                      real3f{f->par.boxSize[0], f->par.boxSize[1], f->par.boxSize[2]}, f->par.viscosity, make_fastdiv(n.x / 2 + 1),
                      make_fastdiv(n.y), 0.0f, true);
-  UH_ROCFFT(rocfft_execute(f->inv, bufs, nullptr, f->info));
+  if (int e = f->fft.inverse(g)) return e;
   hipLaunchKernelGGL((k_fib_midpoint<0>), gp, bp, 0, st, (float4 *)d_pos, (float4 *)f->posOld.ptr, (const float *)g, f->planeReal, f->nxpad, N,
                      f->grid, invh, f->par.dt);
   hipLaunchKernelGGL((k_fib_midpoint<1>), gp, bp, 0, st, (float4 *)d_pos, (float4 *)f->posOld.ptr, (const float *)g, f->planeReal, f->nxpad, N,

@@ -12,25 +12,13 @@
 // reference); here every cell reads the OLD field and writes a second buffer.  The fluid random numbers (cuRAND in the
 // reference) and the initial thermal velocities (System::rng gaussians) come from Saru streams of the handle's seed.
 #include "celllist.hpp"
+#include "rocfft_plans.hpp"
 #include "stagger.hpp"
-
-#include <rocfft/rocfft.h>
 
 #include <algorithm>
 #include <cmath>
 
 namespace uammd_hip {
-
-int rocfft_setup_once();  // fcm.hip
-
-#define UH_ROCFFT(expr)                                                                      \
-  do {                                                                                       \
-    rocfft_status s_ = (expr);                                                               \
-    if (s_ != rocfft_status_success) {                                                       \
-      set_last_error("%s failed with rocfft_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-      return -10 - (int)s_;                                                                  \
-    }                                                                                        \
-  } while (0)
 
 struct ICMState {
   uammd_icm_parameters par{};
@@ -38,33 +26,12 @@ struct ICMState {
   float rh = 0.f, deltaRFD = 0.f;
   int nxpad = 0;
   size_t planeReal = 0, planeCplx = 0;
-  DeviceBuffer velA, velB, advOld, random, posOld, work;
+  DeviceBuffer velA, velB, advOld, random, posOld;
   float *vel = nullptr, *velNext = nullptr;  // vel: v^n (3 padded planes); velNext: scratch the fluid update writes
   const float *externalNoise = nullptr;
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
+  RealFFT fft;
   unsigned int step = 0;
-  ~ICMState() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
 };
-
-static int next_fft_wise_icm(int n) {  // ICM_ns::nextFFTWiseSize3D (ICM.cu:29-84) = utils/Grid.cuh:142-213, one axis
-  static const int primes[5] = {2, 3, 5, 7, 11}, maxExp[5] = {64, 64, 5, 4, 3};
-  for (int c = std::max(n, 1);; ++c) {
-    if (c % 2) continue;
-    int m = c;
-    bool ok = true;
-    for (int p = 0; p < 5; ++p) {
-      int e = 0;
-      while (m % primes[p] == 0) { m /= primes[p]; ++e; }
-      ok = ok && e <= maxExp[p];
-    }
-    if (ok && m == 1) return c;
-  }
-}
 
 // initFluid (:1001-1023): independent N(0, sqrt(kT/(rho dV))) per face
 __global__ void __launch_bounds__(256) k_icm_init(float *__restrict__ v, size_t plane, int nxpad, int3 n, float amp, uint seed) {
@@ -190,36 +157,6 @@ __global__ void __launch_bounds__(256) k_icm_import(float *__restrict__ v, size_
   v[node] = in3[3 * (size_t)ic]; v[plane + node] = in3[3 * (size_t)ic + 1]; v[2 * plane + node] = in3[3 * (size_t)ic + 2];
 }
 
-static int icm_make_plans(ICMState *f) {
-  if (int e = rocfft_setup_once()) return e;
-  const size_t nx = f->grid.cellDim.x, ny = f->grid.cellDim.y, nz = f->grid.cellDim.z, nkx = nx / 2 + 1;
-  const size_t lengths[3] = {nx, ny, nz};
-  const size_t rstr[3] = {1, (size_t)f->nxpad, (size_t)f->nxpad * ny}, cstr[3] = {1, nkx, nkx * ny};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr, nullptr,
-                                                     3, rstr, f->planeReal, 3, cstr, f->planeCplx));
-  UH_ROCFFT(rocfft_plan_create(&f->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_single, 3, lengths,
-                               3, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr, nullptr,
-                                                     3, cstr, f->planeCplx, 3, rstr, f->planeReal));
-  UH_ROCFFT(rocfft_plan_create(&f->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_single, 3, lengths,
-                               3, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(f->fwd, &wf));
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(f->inv, &wi));
-  const size_t w = std::max(wf, wi);
-  UH_ROCFFT(rocfft_execution_info_create(&f->info));
-  if (w) {
-    if (int e = f->work.reserve(w)) return e;
-    UH_ROCFFT(rocfft_execution_info_set_work_buffer(f->info, f->work.ptr, w));
-  }
-  return 0;
-}
-
 }  // namespace uammd_hip
 
 using namespace uammd_hip;
@@ -248,7 +185,7 @@ int uammd_icm_create(const uammd_icm_parameters *par, uammd_icm **out, int cells
   int cd[3] = {par->cells[0], par->cells[1], par->cells[2]};
   if (cd[0] < 0) {
     const float hgrid = (float)(par->hydrodynamicRadius / 0.91);  // :873
-    for (int a = 0; a < 3; ++a) cd[a] = next_fft_wise_icm((int)(par->boxSize[a] / hgrid));
+    for (int a = 0; a < 3; ++a) cd[a] = next_fft_wise((int)(par->boxSize[a] / hgrid));
   }
   if (cd[0] < 3) cd[0] = 3;
   if (cd[1] < 3) cd[1] = 3;
@@ -262,15 +199,13 @@ int uammd_icm_create(const uammd_icm_parameters *par, uammd_icm **out, int cells
   f->grid = make_grid(make_box<float>(par->boxSize, per), make_int3(cd[0], cd[1], cd[2]));
   f->rh = 0.91f * par->boxSize[0] / (float)cd[0];  // getHydrodynamicRadius, ICM.cuh:169-171
   f->deltaRFD = (float)(1e-4 * (double)f->rh);      // single precision build, ICM.cu:844-848
-  f->nxpad = 2 * (cd[0] / 2 + 1);
-  f->planeReal = (size_t)f->nxpad * cd[1] * cd[2];
-  f->planeCplx = (size_t)(cd[0] / 2 + 1) * cd[1] * cd[2];
+  fft_padded_layout(3, cd, &f->nxpad, &f->planeReal, &f->planeCplx);
   const size_t bytes = sizeof(float) * 3 * f->planeReal;
   int e = f->velA.reserve(bytes);
   if (!e) e = f->velB.reserve(bytes);
   if (!e) e = f->advOld.reserve(bytes);
   if (!e && par->temperature != 0.0f) e = f->random.reserve(sizeof(float) * 6 * (size_t)cd[0] * cd[1] * cd[2]);
-  if (!e) e = icm_make_plans(f);
+  if (!e) e = f->fft.create(3, cd, f->nxpad, f->planeReal, f->planeCplx, rocfft_precision_single, 3, 3);
   if (e) { delete f; return e; }
   f->vel = (float *)f->velA.ptr;
   f->velNext = (float *)f->velB.ptr;
@@ -349,14 +284,13 @@ int uammd_icm_fluid_and_corrector(uammd_icm *h, float *d_pos, const float *d_for
   if (f->par.sumThermalDrift && T > 0.0f && N > 0)
     hipLaunchKernelGGL(k_icm_drift, gp, bp, 0, st, (const float4 *)d_pos, g, f->planeReal, f->nxpad, N, f->grid, invh,
                        (dt / rho) * T / f->deltaRFD, f->deltaRFD, f->par.seed, f->step);
-  UH_ROCFFT(rocfft_execution_info_set_stream(f->info, (void *)st));
-  void *bufs[1] = {g};
-  UH_ROCFFT(rocfft_execute(f->fwd, bufs, nullptr, f->info));
+  if (int e = f->fft.set_stream((void *)st)) return e;
+  if (int e = f->fft.forward(g)) return e;
   const uint total = (uint)f->planeCplx;
   hipLaunchKernelGGL((k_fib_stokes<true>), dim3((total + 255) / 256), dim3(256), 0, st, (float2 *)g, f->planeCplx, n,
                      real3f{f->par.boxSize[0], f->par.boxSize[1], f->par.boxSize[2]}, eta, make_fastdiv(n.x / 2 + 1), make_fastdiv(n.y),
                      dt / rho, f->par.removeTotalMomentum != 0);
-  UH_ROCFFT(rocfft_execute(f->inv, bufs, nullptr, f->info));
+  if (int e = f->fft.inverse(g)) return e;
   if (N > 0)
     hipLaunchKernelGGL((k_fib_midpoint<1>), gp, bp, 0, st, (float4 *)d_pos, (float4 *)f->posOld.ptr, (const float *)g, f->planeReal, f->nxpad,
                        N, f->grid, invh, dt);

@@ -12,8 +12,7 @@
 // runs one thread per Morton-sorted particle over a packed (x, y, z, q) array in the reference's neighbour order.
 #include "celllist.hpp"
 #include "ibm.hpp"
-
-#include <rocfft/rocfft.h>
+#include "rocfft_plans.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -21,17 +20,6 @@
 #include <vector>
 
 namespace uammd_hip {
-
-int rocfft_setup_once();  // fcm.hip
-
-#define UH_ROCFFT(expr)                                                                      \
-  do {                                                                                       \
-    rocfft_status s_ = (expr);                                                               \
-    if (s_ != rocfft_status_success) {                                                       \
-      set_last_error("%s failed with rocfft_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-      return -10 - (int)s_;                                                                  \
-    }                                                                                        \
-  } while (0)
 
 struct Poisson {
   uammd_poisson_parameters par{};
@@ -44,7 +32,7 @@ struct Poisson {
   size_t planeReal = 0, planeCplx = 0;
   float cutoff = 0.f;
   int ntable = 0;
-  DeviceBuffer tableField, tablePotential, gridQ, planes, inter, packed, work;
+  DeviceBuffer tableField, tablePotential, gridQ, planes, inter, packed;
   // tile-owned spread: tile dimensions (divisors of the grid, >= support-1), particles binned by the tile of their
   // stencil origin
   struct TileSet {
@@ -57,13 +45,7 @@ struct Poisson {
   TileSet spreadTiles;
   bool forceAtomicSpread = false;
   CellList cl;
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
-  ~Poisson() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
+  RealFFT fft;
 };
 
 // ---- host: closed forms and heuristics (double arithmetic on float arguments, as the reference's host code) ----------
@@ -106,21 +88,6 @@ static double far_width(float gw, float split) {
   double w = gw;
   if (split > 0) w = sqrt(gw * gw + 1.0 / (4.0 * split * split));
   return w;
-}
-// nextFFTWiseSize3D (utils/Grid.cuh:142-213): smallest even 2^a 3^b 5^c 7^d 11^e >= n with c<=5, d<=4, e<=3
-static int next_fft_wise(int n) {
-  static const int primes[5] = {2, 3, 5, 7, 11}, maxExp[5] = {64, 64, 5, 4, 3};
-  for (int c = std::max(n, 1);; ++c) {
-    if (c % 2) continue;
-    int m = c;
-    bool ok = true;
-    for (int p = 0; p < 5; ++p) {
-      int e = 0;
-      while (m % primes[p] == 0) { m /= primes[p]; ++e; }
-      ok = ok && e <= maxExp[p];
-    }
-    if (ok && m == 1) return c;
-  }
 }
 
 // ---- device ------------------------------------------------------------------------------------------------------
@@ -701,37 +668,6 @@ static Table1 view(const DeviceBuffer &b, int ntable, float rmax) {
   return t;
 }
 
-static int poisson_make_plans(Poisson *p) {
-  if (int e = rocfft_setup_once()) return e;
-  const size_t nx = p->cells[0], ny = p->cells[1], nz = p->cells[2], nkx = nx / 2 + 1;
-  const size_t lengths[3] = {nx, ny, nz};
-  const size_t rstr[3] = {1, (size_t)p->nxpad, (size_t)p->nxpad * ny};
-  const size_t cstr[3] = {1, nkx, nkx * ny};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                     nullptr, 3, rstr, p->planeReal, 3, cstr, p->planeCplx));
-  UH_ROCFFT(rocfft_plan_create(&p->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_single, 3,
-                               lengths, 1, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                                                     nullptr, 3, cstr, p->planeCplx, 3, rstr, p->planeReal));
-  UH_ROCFFT(rocfft_plan_create(&p->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_single, 3,
-                               lengths, 4, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(p->fwd, &wf));
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(p->inv, &wi));
-  const size_t w = std::max(wf, wi);
-  UH_ROCFFT(rocfft_execution_info_create(&p->info));
-  if (w) {
-    if (int e = p->work.reserve(w)) return e;
-    UH_ROCFFT(rocfft_execution_info_set_work_buffer(p->info, p->work.ptr, w));
-  }
-  return 0;
-}
-
 // counting sort of the packed particles by the tile of their stencil origin
 static int poisson_bin(Poisson *p, Poisson::TileSet &ts, int N, hipStream_t st) {
   const int nt = ts.numTiles();
@@ -782,16 +718,14 @@ static int poisson_far(Poisson *p, int N, float *d_force, float *d_energy, float
     hipLaunchKernelGGL(k_poisson_spread, dim3((N + 3) / 4), dim3(256), 0, st, (const float4 *)p->packed.ptr, gq, N, p->grid,
                        p->nxpad, p->kern, dsx, dsxy);
   }
-  UH_ROCFFT(rocfft_execution_info_set_stream(p->info, (void *)st));
-  void *bq[1] = {gq};
-  UH_ROCFFT(rocfft_execute(p->fwd, bq, nullptr, p->info));
+  if (int e = p->fft.set_stream((void *)st)) return e;
+  if (int e = p->fft.forward(gq)) return e;
   const int3 n = p->grid.cellDim;
   const int nkx = n.x / 2 + 1;
   const uint total = (uint)p->planeCplx;
   hipLaunchKernelGGL(k_poisson_convolve, dim3((total + 255) / 256), dim3(256), 0, st, (const float2 *)gq, (float2 *)p->planes.ptr,
                      p->planeCplx, n, real3f{p->L[0], p->L[1], p->L[2]}, p->par.epsilon, make_fastdiv(nkx), make_fastdiv(n.y));
-  void *bp[1] = {p->planes.ptr};
-  UH_ROCFFT(rocfft_execute(p->inv, bp, nullptr, p->info));
+  if (int e = p->fft.inverse(p->planes.ptr)) return e;
   const uint nreal = (uint)p->planeReal;
   hipLaunchKernelGGL(k_poisson_interleave, dim3((nreal + 255) / 256), dim3(256), 0, st, (const float *)p->planes.ptr, p->planeReal,
                      (float4 *)p->inter.ptr, nreal);
@@ -929,13 +863,11 @@ int uammd_poisson_create(const uammd_poisson_parameters *par, uammd_poisson **ou
       return -4;
     }
   }
-  p->nxpad = 2 * (p->cells[0] / 2 + 1);
-  p->planeReal = (size_t)p->nxpad * p->cells[1] * p->cells[2];
-  p->planeCplx = (size_t)(p->cells[0] / 2 + 1) * p->cells[1] * p->cells[2];
+  fft_padded_layout(3, p->cells, &p->nxpad, &p->planeReal, &p->planeCplx);
   int e = p->gridQ.reserve(sizeof(float) * p->planeReal);
   if (!e) e = p->planes.reserve(sizeof(float) * 4 * p->planeReal);
   if (!e) e = p->inter.reserve(sizeof(float4) * p->planeReal);
-  if (!e) e = poisson_make_plans(p);
+  if (!e) e = p->fft.create(3, p->cells, p->nxpad, p->planeReal, p->planeCplx, rocfft_precision_single, 1, 4);
   // Spread tiles: per axis the divisor of the grid in [4, 12] closest to 8, as many private float copies (waves) as fit 64 KB.
   // (An LDS-tile GATHER of the float4 grid was built too: the halo-extended float4 tile only fits for 4-node-thick tiles,
   // whose 12-27x halo reload made it no faster than the global gather — 1.2-1.9 ms against 1.6 ms — so it was dropped.)

@@ -12,25 +12,13 @@
 // ik.y = 0, .cu:425-428); that write is not reproduced.
 #include "celllist.hpp"
 #include "ibm.hpp"
+#include "rocfft_plans.hpp"
 #include "saru.hpp"
-
-#include <rocfft/rocfft.h>
 
 #include <algorithm>
 #include <cmath>
 
 namespace uammd_hip {
-
-int rocfft_setup_once();  // fcm.hip
-
-#define UH_ROCFFT(expr)                                                                      \
-  do {                                                                                       \
-    rocfft_status s_ = (expr);                                                               \
-    if (s_ != rocfft_status_success) {                                                       \
-      set_last_error("%s failed with rocfft_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-      return -10 - (int)s_;                                                                  \
-    }                                                                                        \
-  } while (0)
 
 struct BDHI2D {
   uammd_bdhi2d_parameters par{};
@@ -38,31 +26,10 @@ struct BDHI2D {
   IBMKernelDev kern{}, kernDriftX{}, kernDriftY{};
   int nxpad = 0;
   size_t planeReal = 0, planeCplx = 0;
-  DeviceBuffer gridBuf, work;
-  rocfft_plan fwd = nullptr, inv = nullptr;
-  rocfft_execution_info info = nullptr;
+  DeviceBuffer gridBuf;
+  RealFFT fft;
   unsigned int counter = 0;  // the reference's `static ullint counter` (.cu:455), per handle here
-  ~BDHI2D() {
-    if (fwd) rocfft_plan_destroy(fwd);
-    if (inv) rocfft_plan_destroy(inv);
-    if (info) rocfft_execution_info_destroy(info);
-  }
 };
-
-int next_fft_wise_axis(int n) {  // nextFFTWiseSize3D (utils/Grid.cuh:142-213), one axis
-  static const int primes[5] = {2, 3, 5, 7, 11}, maxExp[5] = {64, 64, 5, 4, 3};
-  for (int c = std::max(n, 1);; ++c) {
-    if (c % 2) continue;
-    int m = c;
-    bool ok = true;
-    for (int p = 0; p < 5; ++p) {
-      int e = 0;
-      while (m % primes[p] == 0) { m /= primes[p]; ++e; }
-      ok = ok && e <= maxExp[p];
-    }
-    if (ok && m == 1) return c;
-  }
-}
 
 // BDHI2D_ns::True2D / Quasi2D::operator() (.cuh:88-92, :100-109)
 UH_D float2 hydro_kernel(int mode, float k2, float a) {
@@ -203,36 +170,6 @@ __global__ void __launch_bounds__(256) k_q2d_update(float4 *__restrict__ pos, co
   pos[i] = p;
 }
 
-static int q2d_make_plans(BDHI2D *q) {
-  if (int e = rocfft_setup_once()) return e;
-  const size_t nx = q->grid.cellDim.x, ny = q->grid.cellDim.y, nkx = nx / 2 + 1;
-  const size_t len[2] = {nx, ny};
-  const size_t rstr[2] = {1, (size_t)q->nxpad}, cstr[2] = {1, nkx};
-  rocfft_plan_description d = nullptr;
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                     nullptr, 2, rstr, q->planeReal, 2, cstr, q->planeCplx));
-  UH_ROCFFT(rocfft_plan_create(&q->fwd, rocfft_placement_inplace, rocfft_transform_type_real_forward, rocfft_precision_single, 2, len,
-                               2, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  UH_ROCFFT(rocfft_plan_description_create(&d));
-  UH_ROCFFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                                                     nullptr, 2, cstr, q->planeCplx, 2, rstr, q->planeReal));
-  UH_ROCFFT(rocfft_plan_create(&q->inv, rocfft_placement_inplace, rocfft_transform_type_real_inverse, rocfft_precision_single, 2, len,
-                               2, d));
-  UH_ROCFFT(rocfft_plan_description_destroy(d));
-  size_t wf = 0, wi = 0;
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(q->fwd, &wf));
-  UH_ROCFFT(rocfft_plan_get_work_buffer_size(q->inv, &wi));
-  const size_t w = std::max(wf, wi);
-  UH_ROCFFT(rocfft_execution_info_create(&q->info));
-  if (w) {
-    if (int e = q->work.reserve(w)) return e;
-    UH_ROCFFT(rocfft_execution_info_set_work_buffer(q->info, q->work.ptr, w));
-  }
-  return 0;
-}
-
 }  // namespace uammd_hip
 
 using namespace uammd_hip;
@@ -255,8 +192,8 @@ int uammd_bdhi2d_create(const uammd_bdhi2d_parameters *par, uammd_bdhi2d **out, 
   if (cd[0] <= 0) {  // initializeGrid, .cu:61-73
     const double h = a * 0.8;
     const float hr = (float)h;
-    cd[0] = next_fft_wise_axis((int)(par->boxSize[0] / hr));
-    cd[1] = next_fft_wise_axis((int)(par->boxSize[1] / hr));
+    cd[0] = next_fft_wise((int)(par->boxSize[0] / hr));
+    cd[1] = next_fft_wise((int)(par->boxSize[1] / hr));
   }
   const float L3[3] = {par->boxSize[0], par->boxSize[1], 0.0f};
   const int per[3] = {1, 1, 0};
@@ -285,11 +222,9 @@ int uammd_bdhi2d_create(const uammd_bdhi2d_parameters *par, uammd_bdhi2d **out, 
   q->kernDriftX = to_dev(k);
   k.kind = UAMMD_IBM_KERNEL_GAUSS2D_DRIFT_Y;
   q->kernDriftY = to_dev(k);
-  q->nxpad = 2 * (cd[0] / 2 + 1);
-  q->planeReal = (size_t)q->nxpad * cd[1];
-  q->planeCplx = (size_t)(cd[0] / 2 + 1) * cd[1];
+  fft_padded_layout(2, cd, &q->nxpad, &q->planeReal, &q->planeCplx);
   int e = q->gridBuf.reserve(sizeof(float) * 2 * q->planeReal);
-  if (!e) e = q2d_make_plans(q);
+  if (!e) e = q->fft.create(2, cd, q->nxpad, q->planeReal, q->planeCplx, rocfft_precision_single, 2, 2);
   if (e) { delete q; return e; }
   if (cells) { cells[0] = cd[0]; cells[1] = cd[1]; }
   if (support) *support = s;
@@ -315,8 +250,7 @@ int uammd_bdhi2d_velocities(uammd_bdhi2d *h, const float *d_pos, const float *d_
   const dim3 gp((N + 3) / 4), bp(256);
   const FastDiv dsx = make_fastdiv(q->kern.support.x);
   const int nx = q->grid.cellDim.x, ny = q->grid.cellDim.y;
-  UH_ROCFFT(rocfft_execution_info_set_stream(q->info, (void *)st));
-  void *bufs[1] = {g};
+  if (int e = q->fft.set_stream((void *)st)) return e;
   if (deterministic) {
     UH_CHECK(hipMemsetAsync(g, 0, sizeof(float) * 2 * q->planeReal, st));
     if (drift) {  // spreadThermalDrift, .cu:234-257
@@ -328,7 +262,7 @@ int uammd_bdhi2d_velocities(uammd_bdhi2d *h, const float *d_pos, const float *d_
     if (d_force)  // spreadParticleForces, .cu:268-283
       hipLaunchKernelGGL((k_q2d_ibm<true, kKernelGauss2D>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)d_force, 0.0f, 0.0f, g, q->planeReal,
                          (float2 *)nullptr, N, q->grid, q->nxpad, q->kern, dsx);
-    UH_ROCFFT(rocfft_execute(q->fwd, bufs, nullptr, q->info));
+    if (int e = q->fft.forward(g)) return e;
   }
   if (!deterministic && !(T > 0)) {  // nothing moves the particles
     UH_CHECK(hipMemsetAsync(d_vel, 0, sizeof(float) * 2 * (size_t)N, st));
@@ -343,7 +277,7 @@ int uammd_bdhi2d_velocities(uammd_bdhi2d *h, const float *d_pos, const float *d_
   hipLaunchKernelGGL(k_q2d_kspace, dim3((total + 255) / 256), dim3(256), 0, st, (float2 *)g, (float2 *)g + q->planeCplx, nx, ny,
                      q->par.boxSize[0], q->par.boxSize[1], q->par.kernel, q->par.hydrodynamicRadius, q->par.viscosity, deterministic,
                      noisePrefactor, q->par.seed, q->counter);
-  UH_ROCFFT(rocfft_execute(q->inv, bufs, nullptr, q->info));
+  if (int e = q->fft.inverse(g)) return e;
   hipLaunchKernelGGL((k_q2d_ibm<false, kKernelGauss2D>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)nullptr, 0.0f, 0.0f, g, q->planeReal,
                      (float2 *)d_vel, N, q->grid, q->nxpad, q->kern, dsx);
   UH_CHECK(hipGetLastError());
