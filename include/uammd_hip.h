@@ -193,6 +193,30 @@ int uammd_lj_transverse_nbody(const float *d_pos, int numberParticles, const uam
                               float *d_energy, float *d_virial, const int *d_globalIndex, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Potential::DPD (Interactor/Potential/DPD.cuh): PairForces<Potential::DPD> on the cell list and on all pairs
+ *
+ * Replaces DPD_impl::ForceTransverser::compute / getInfo / set (DPD.cuh:121-158) run by CellList::transverseList
+ * (PairForces.cu:55-68) and by NBody (PairForces.cu:49-53).  Per pair within the cut-off, in float:
+ *   rij = pbc(ri - rj), vij = vi - vj, wr = 1 - r/cutOff
+ *   F_i += (A wr / r  -  gamma wr^2 (rij . vij) / r^2  +  xi sigma sqrt(gamma) wr / r) rij
+ *   xi = Saru(min(i,j) + numberParticlesKey max(i,j), seed, step).gf(0, 1).x      (key in unsigned arithmetic, seed and step
+ *                                                                                   truncated to 32 bits as Saru's constructor does)
+ * i, j are the particles' indices in d_vel / d_force (what getInfo receives); with d_globalIndex (group -> global, nullable) the list's
+ * or the loop's member t is particle d_globalIndex[t].  sigma = sqrt(2 kT) / sqrt(dt) is the caller's (DPD.cuh:69); numberParticlesKey
+ * is pd->getNumParticles() (DPD.cuh:167).  d_vel is real3[.] in input order; d_force real4[.] is ACCUMULATED at the particle's index
+ * (set does +=, DPD.cuh:156-158).  Every particle sums its own pairs in a fixed order: no atomics, the same bits run to run.
+ * Energy and virial are not defined for DPD (DPD.cuh:171-180).
+ * The list variant gathers {velocity, index} into list order once per call, into scratch memory the handle owns (allocated on the
+ * first call of a size); it needs a list whose cells are at least cutOff wide (uammd_celllist_create_grid with that cut-off). */
+int uammd_dpd_transverse_celllist(uammd_celllist *h, const float *d_vel, const float boxL[3], const int boxPeriodic[3], float cutOff,
+                                  float A, float gamma, float sigma, unsigned long long seed, unsigned long long step,
+                                  int numberParticlesKey, float *d_force, const int *d_globalIndex, void *stream);
+/* d_pos is the UN-gathered real4 array: member t reads d_pos[d_globalIndex[t]] (NBody over the group's iterators) */
+int uammd_dpd_transverse_nbody(const float *d_pos, const float *d_vel, int numberParticles, const float boxL[3], const int boxPeriodic[3],
+                               float cutOff, float A, float gamma, float sigma, unsigned long long seed, unsigned long long step,
+                               int numberParticlesKey, float *d_force, const int *d_globalIndex, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Path A — Verlet list.  Replaces
  *   VerletListBase::{update,needsRebuild,getVerletList,setCutOffMultiplier,forceNextUpdate,getNumberOfStepsSinceLastUpdate}
  *                                                               Interactor/NeighbourList/VerletList/VerletListBase.cuh:73-199
@@ -273,6 +297,11 @@ int uammd_lj_transverse_celllist_gj2(uammd_celllist *h, const uammd_lj_pair_para
 int uammd_verletnvt_basic(int step, float *d_pos, float *d_vel, float *d_force, const float *d_mass,
                           float defaultMass, const int *d_index, int numberParticles, float dt, float friction,
                           int is2D, float noiseAmplitude, unsigned int stepNum, unsigned int seed, void *stream);
+/* VerletNVE_ns::integrateGPU<step> (Integrator/VerletNVE.cu:64-85): vel += force / m * dt / 2, vel.z = 0 if is2D, and in step 1
+ * pos += vel * dt.  m = d_mass[i] whenever d_mass is given, else defaultMass (:76).  The forces are read only: zeroing them between the
+ * two halves is the caller's (VerletNVE::resetForces, :152-158).  d_index (group -> global, nullable). */
+int uammd_verletnve(int step, float *d_pos, float *d_vel, const float *d_force, const float *d_mass, float defaultMass,
+                    const int *d_index, int numberParticles, float dt, int is2D, void *stream);
 int uammd_verletnvt_initial_velocities(float *d_vel, const int *d_index, float velAmplitude, int is2D,
                                        int numberParticles, unsigned int seed, void *stream);
 /* VerletNVT::Basic::sumKineticEnergy (VerletNVT/Basic.cu:173-207): energy[i] += 0.5 m |v|^2 (Integrator::sumEnergy) */

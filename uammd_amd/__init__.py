@@ -15,6 +15,7 @@ from .hydro import Hydro  # noqa: F401
 from .checkpoint import restoreParticleData, saveParticleData  # noqa: F401
 from .bdhi import BDHI, IBM, FCMKernels, Kernels, nextFFTWiseSize3D  # noqa: F401
 from .bonded import AngularBondedForces, BondedForces, BondedType, TorsionalBondedForces  # noqa: F401
+from .dpd import DPD, VerletNVE  # noqa: F401  (Potential.DPD is the same class)
 
 __all__ = ["UammdHipError", "load", "Box", "ParticleData", "ParticleGroup", "CellList", "VerletList", "Potential", "PairForces", "Interactor",
-           "Integrator", "VerletNVT", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream"]
+           "Integrator", "VerletNVT", "VerletNVE", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream"]

@@ -193,6 +193,9 @@ SIGNATURES = {
     "uammd_verletnvt_gj_lj_step": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _f3, _i3, _f3, _i3, _i3, _vp, _i, _f, _f, _i, _f, _u, _u, _i, _vp]),
     "uammd_verletnvt_basic": (_i, [_i, _vp, _vp, _vp, _vp, _f, _vp, _i, _f, _f, _i, _f, _u, _u, _vp]),
     "uammd_verletnvt_initial_velocities": (_i, [_vp, _vp, _f, _i, _i, _u, _vp]),
+    "uammd_verletnve": (_i, [_i, _vp, _vp, _vp, _vp, _f, _vp, _i, _f, _i, _vp]),
+    "uammd_dpd_transverse_celllist": (_i, [_vp, _vp, _f3, _i3, _f, _f, _f, _f, C.c_ulonglong, C.c_ulonglong, _i, _vp, _vp, _vp]),
+    "uammd_dpd_transverse_nbody": (_i, [_vp, _vp, _i, _f3, _i3, _f, _f, _f, _f, C.c_ulonglong, C.c_ulonglong, _i, _vp, _vp, _vp]),
     "uammd_sum_kinetic_energy": (_i, [_vp, _vp, _vp, _f, _vp, _i, _vp]),
     "uammd_bd_euler_maruyama": (_i, [_vp, _vp, _vp, C.POINTER(_f), _f, _vp, _f, _i, _f, _i, _u, _u, _vp]),
     "uammd_fcm_euler_maruyama": (_i, [_vp, _vp, _vp, _i, _f, _vp]),

@@ -84,6 +84,7 @@ struct CellList {
   } prof;
   DeviceBuffer tileStats;  // uammd_lj_tile_stats: counters the tile kernel bumps while enabled
   bool tileStatsOn = false;
+  DeviceBuffer dpdVel;  // uammd_dpd_transverse_celllist: {velocity, particle index} rows in list order, gathered once per sum (dpd.hip)
   int numOwned = 0x7fffffff;  // traversal option: particles with input index >= numOwned are ghosts (neighbours only, no output)
 
   int next_valid_cell(int numberParticles, bool *needsClear);

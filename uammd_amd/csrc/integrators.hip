@@ -5,6 +5,7 @@
 //   VerletNVT::GronbechJensen_ns::integrateGPU<step>   Integrator/VerletNVT/GronbechJensen.cu:28-62
 //   VerletNVT::Basic_ns::integrateGPU<step>            Integrator/VerletNVT/Basic.cu:86-114
 //   VerletNVT::Basic_ns::initialVelocities             Integrator/VerletNVT/Basic.cu:12-29
+//   VerletNVE_ns::integrateGPU<step>                   Integrator/VerletNVE.cu:64-85
 //   BD::EulerMaruyama_ns::integrateGPU                 Integrator/BrownianDynamics.cu:119-144
 //   BDHI::FCM_ns::integrateEulerMaruyamaD              Integrator/BDHI/BDHI_FCM.cu:67-92
 // Noise streams are keyed exactly as in the reference: Saru(thread index in group, step, seed).
@@ -111,6 +112,32 @@ __global__ void __launch_bounds__(kIB) k_sum_kinetic_energy(const float *__restr
   const float m = (defaultMass > 0.f || !mass) ? defaultMass : mass[i];
   const float v2 = __fmaf_rn(vz, vz, __fmaf_rn(vy, vy, vx * vx));
   energy[i] += 0.5f * v2 * m;
+}
+
+// VerletNVE_ns::integrateGPU<step> (Integrator/VerletNVE.cu:64-85): half kick, vel.z = 0 in 2-D, drift in step 1 only.  The mass array
+// wins over defaultMass whenever it is there (:76) — unlike sumEnergy (:203-224), where defaultMass > 0 wins.
+template <int STEP>
+__global__ void __launch_bounds__(kIB) k_verletnve(float4 *__restrict__ pos, float *__restrict__ vel, const float4 *__restrict__ force,
+                                                   const float *__restrict__ mass, float defaultMass, const int *__restrict__ index, int N,
+                                                   float dt, int is2D) {
+  const int id = blockIdx.x * kIB + threadIdx.x;
+  if (id >= N) return;
+  const int i = index ? index[id] : id;
+  const float m = mass ? mass[i] : defaultMass;
+  const float4 f = force[i];
+  float3 v = make_float3(vel[3 * i], vel[3 * i + 1], vel[3 * i + 2]);
+  v.x = v.x + (f.x / m) * dt * 0.5f;
+  v.y = v.y + (f.y / m) * dt * 0.5f;
+  v.z = v.z + (f.z / m) * dt * 0.5f;
+  if (is2D) v.z = 0.0f;
+  vel[3 * i] = v.x; vel[3 * i + 1] = v.y; vel[3 * i + 2] = v.z;
+  if (STEP == 1) {
+    float4 p = pos[i];
+    p.x = p.x + v.x * dt;
+    p.y = p.y + v.y * dt;
+    p.z = p.z + v.z * dt;
+    pos[i] = p;
+  }
 }
 
 struct Shear { float3 Kx, Ky, Kz; };
@@ -335,6 +362,23 @@ int uammd_verletnvt_basic(int step, float *d_pos, float *d_vel, float *d_force, 
   else
     hipLaunchKernelGGL(k_verletnvt_basic<2>, dim3(nb(N)), dim3(kIB), 0, st, (float4 *)d_pos, d_vel, (float4 *)d_force,
                        d_mass, defaultMass, d_index, N, dt, friction, is2D, noiseAmplitude, stepNum, seed);
+  UH_CHECK(hipGetLastError());
+  return 0;
+}
+
+int uammd_verletnve(int step, float *d_pos, float *d_vel, const float *d_force, const float *d_mass, float defaultMass, const int *d_index,
+                    int N, float dt, int is2D, void *stream) {
+  if (N <= 0) return 0;
+  if (!d_pos || !d_vel || !d_force) { set_last_error("uammd_verletnve: null argument"); return -1; }
+  if (step != 1 && step != 2) { set_last_error("uammd_verletnve: step must be 1 or 2"); return -1; }
+  if (!d_mass && !(defaultMass > 0)) { set_last_error("uammd_verletnve: no mass array and defaultMass <= 0"); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  if (step == 1)
+    hipLaunchKernelGGL(k_verletnve<1>, dim3(nb(N)), dim3(kIB), 0, st, (float4 *)d_pos, d_vel, (const float4 *)d_force, d_mass, defaultMass,
+                       d_index, N, dt, is2D);
+  else
+    hipLaunchKernelGGL(k_verletnve<2>, dim3(nb(N)), dim3(kIB), 0, st, (float4 *)d_pos, d_vel, (const float4 *)d_force, d_mass, defaultMass,
+                       d_index, N, dt, is2D);
   UH_CHECK(hipGetLastError());
   return 0;
 }

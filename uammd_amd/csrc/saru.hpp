@@ -82,6 +82,19 @@ struct Saru {
     return gf(mean, std);  // (host pass of the compiler only)
 #endif
   }
+  // The first member (.x, the sine branch) of gf_fast's pair alone, for callers that throw the second away (the DPD pair force draws one
+  // normal per pair, DPD.cuh:150): the same two uniforms are consumed, the cosine is not computed.
+  UH_HD float gf_fast_x(float mean, float std) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float u0;
+    do { u0 = f(); } while (u0 <= 1.17549435e-38f);
+    const float u1 = f();
+    const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u0));
+    return fmaf(r * __builtin_amdgcn_sinf(u1), std, mean);
+#else
+    return gf(mean, std).x;
+#endif
+  }
 };
 
 }  // namespace uammd_hip

@@ -54,6 +54,28 @@ class Xorshift128plus:
     def next32(self):
         return self.next() % 0xFFFFFFFF
 
+    def uniform(self, lo, hi):
+        return lo + (float(self.next()) / float(0xFFFFFFFFFFFFFFFF)) * (hi - lo)
+
+    _spare, _have_spare = 0.0, False   # (one spare for every generator of the process, as utils/utils.h:77-104 has it)
+
+    def gaussian(self, mean, std):
+        """Box-Muller, two numbers per pair of uniforms: the second is handed out by the next call (utils/utils.h:77-104)."""
+        cls = Xorshift128plus
+        cls._have_spare = not cls._have_spare
+        if not cls._have_spare:
+            return cls._spare * std + mean
+        while True:
+            u1, u2 = self.uniform(0.0, 1.0), self.uniform(0.0, 1.0)
+            if u1 > 2.2250738585072014e-308:
+                break
+        r, phi = math.sqrt(-2.0 * math.log(u1)), 2.0 * math.pi * u2
+        cls._spare = r * math.sin(phi)
+        return r * math.cos(phi) * std + mean
+
+    def gaussian3(self, mean, std):
+        return (self.gaussian(mean, std), self.gaussian(mean, std), self.gaussian(mean, std))
+
 
 class Box:
     def __init__(self, L, periodic=(True, True, True)):
@@ -601,7 +623,29 @@ class PairForces(Interactor):
         cd, ubox = CellList.create_update_grid(self.box, rc)
         return self.nl, self.box, ubox, cd, self.pot.device_table(), self.pot.ntypes, self.algo
 
+    # ParameterUpdatableDelegate<Potential> (PairForces.cuh:25,40-44): a potential that listens hears what PairForces hears
+    def _forward(self, name, value):
+        fn = getattr(self.pot, name, None)
+        if fn is not None:
+            fn(value)
+
+    def updateSimulationTime(self, t):
+        self._forward("updateSimulationTime", t)
+
+    def updateTimeStep(self, dt):
+        self._forward("updateTimeStep", dt)
+
+    def updateTemperature(self, T):
+        self._forward("updateTemperature", T)
+
+    def updateBox(self, box):
+        self.box = box
+        self._forward("updateBox", box)
+
     def sum(self, force=True, energy=False, virial=False):
+        own = getattr(self.pot, "sum_pair_forces", None)
+        if own is not None:   # a potential with a traversal of its own in the library (Potential.DPD, dpd.py)
+            return own(self, force, energy, virial)
         pd = self.pd
         f = pd.getForce("readwrite") if force else None
         e = pd.getEnergy("readwrite") if energy else None
