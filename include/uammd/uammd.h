@@ -80,6 +80,7 @@ namespace uammd {
 
 using std::make_shared;
 using std::shared_ptr;
+using std::string;  // System/System.h:34: programs say `string` after `using namespace uammd`
 
 // ---- global/defines.h:33-44, utils/vector.cuh: real, real2/3/4, int2/3 and their arithmetic (own headers at the reference's paths) ----
 // ---- errors: utils/debugTools.h:20-64, utils/exception.h ---------------------------------------------------------

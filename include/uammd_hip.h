@@ -254,6 +254,28 @@ int uammd_lj_transverse_verletlist(uammd_verletlist *h, const uammd_lj_pair_para
                                    float *d_virial, const int *d_globalIndex, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SPH (Interactor/SPH.cuh): the density and the force sums of smoothed particle hydrodynamics over an UPDATED Verlet list
+ *
+ * Replaces SPH::sum (SPH.cu:178-215): DensityTransverser, the Density2Pressure transform and ForceTransverser, with the M4 cubic spline
+ * of SPH/Kernel.cuh.  In float, with h = support, m = d_mass or 1, rij = pbc(rj - ri), r = |rij|, vij = vj - vi and j over the list
+ * entries of i (i itself included: the self term counts in the density):
+ *   W: q = r / h;      0 if q >= 2;  ((2 - q)^3 - [q <= 1] 4 (1 - q)^3) / (4 pi h^3)
+ *   G: q = r (1 / h);  0 if q >= 2;  c (3 r - 4 h) rij if q <= 1, else c (2 h - r)^2 rij;  c = -3 / (4 pi h^6)   (as the reference writes it)
+ *   rho_i = sum_j m_j W;  P_i = gasStiffness (rho_i - restDensity)
+ *   F_i += sum_j m_i m_j (P_i / rho_i^2 + P_j / rho_j^2 - viscosity (vij . rij) / (r^2 + 0.001 h^2)) G
+ * The list must have been updated (uammd_verletlist_update) with a cut-off of at least 2 support on the positions of this state; -3
+ * otherwise.  d_vel real3[N] and d_mass real[N] (nullable) are in the order of the positions the list was updated with; d_force real4[N]
+ * is ACCUMULATED at the particle's index, .w untouched; d_density / d_pressure real[N] (nullable) receive rho and P in the same order.
+ * Two launches, one lane per particle, no atomics: the same bits run to run.  Scratch rows ({velocity, P / rho^2} and mass in list
+ * order) belong to the handle and are allocated on the first call of a size.  No energy or virial is defined.  -1 on null arguments or
+ * support <= 0; an empty list returns 0. */
+int uammd_sph_sum_verletlist(uammd_verletlist *h, const float *d_vel /*real3[N]*/, const float *d_mass /*nullable*/,
+                             const float boxL[3], const int boxPeriodic[3], float support, float viscosity,
+                             float gasStiffness, float restDensity, float *d_force /*real4[N], accumulated*/,
+                             float *d_density /*nullable out, particle order*/, float *d_pressure /*nullable out*/,
+                             void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Integrator kernels.  Replace
  *   VerletNVT::GronbechJensen_ns::integrateGPU<step>   Integrator/VerletNVT/GronbechJensen.cu:28-62
  *   VerletNVT::Basic_ns::integrateGPU<step>            Integrator/VerletNVT/Basic.cu:86-114

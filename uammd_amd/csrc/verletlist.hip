@@ -10,31 +10,12 @@
 // 27-cell walk, entry k at neighbourList[k*N + i] (lanes of a wave write/read consecutive addresses); capacity starts at
 // 32 per particle and grows by 32 until no particle reaches it; the list is rebuilt when any particle has moved
 // >= (1.08 rc - rc)/2 from its stored position; sortPos is refreshed from the current positions at every update.
-#include "celllist.hpp"
+#include "verletlist.hpp"
 #include "lj_common.hpp"
 
 #include <string>
 
 namespace uammd_hip {
-
-struct VerletList {
-  CellList cl;  // BasicNeighbourListBase::cl
-  DeviceBuffer neighbourList, numberNeighbours, storedPos, sortPos, flags;
-  int maxNeighboursPerParticle = 32;      // BasicListBase.cuh:127
-  float verletRadiusMultiplier = 1.08f;   // VerletListBase.cuh:101
-  float currentCutOff = 0.0f;
-  float boxL[3] = {0, 0, 0};
-  int boxPeriodic[3] = {0, 0, 0};
-  bool haveBox = false;
-  int storedN = -1;
-  bool forceNextRebuild = true;
-  int stepsSinceLastUpdate = 0;
-  int N = 0;
-  uint *hostFlag = nullptr;  // pinned: the drift / overflow flags are read back every update, as in the reference
-  ~VerletList() {
-    if (hostFlag) (void)hipHostFree(hostFlag);
-  }
-};
 
 // K7.  One thread per sorted particle; the walk is the cell list's (x fastest, then y, z; particles ascending).
 // Entry k of particle i lives at neighbourList[k*N + i]: a row k is contiguous over i, but the lanes of a wave reach a
