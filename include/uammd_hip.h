@@ -137,7 +137,10 @@ int uammd_celllist_set_option(uammd_celllist *h, const char *name, int value);
 /* library-wide tunables (measurement switches; an unknown name or a bad value is an error):
  *   "bonded_baseline" = 1        uammd_bonded_sum runs the reference-shaped kernel (thread per particle, AoS entries, id2index looked up
  *                                on every step, BondedForces.cu:191-246); 0 (default) the CSR kernels
- *   "bonded_wave_threshold" = T  rows with more than T entries take the wave-per-row shape (default 32) */
+ *   "bonded_wave_threshold" = T  rows with more than T entries take the wave-per-row shape (default 32)
+ *   "mc_baseline" = 1            uammd_mc_anderson_step runs the reference-shaped kernel (thread per cell, Anderson.cu:302-349); 0 (default)
+ *                                the wave-per-cell kernel with the neighbourhood staged in LDS
+ *   "mc_stage_capacity" = R      rows of LDS a wave of that kernel stages (default 512, 0..960) */
 int uammd_hip_set_tunable(const char *name, int value);
 
 /* ParticleSorter::updateOrderWithCustomHash + applyCurrentOrder building blocks
@@ -274,6 +277,45 @@ int uammd_sph_sum_verletlist(uammd_verletlist *h, const float *d_vel /*real3[N]*
                              float gasStiffness, float restDensity, float *d_force /*real4[N], accumulated*/,
                              float *d_density /*nullable out, particle order*/, float *d_pressure /*nullable out*/,
                              void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Monte Carlo NVT on a checkerboard (Integrator/MonteCarlo/NVT/Anderson.cuh, Anderson.cu) with Potential::LJ
+ *
+ * Replaces one MC_NVT::Anderson<LJ>::forwardTime minus its host draws, which stay with the caller so that every front end takes them
+ * from its System::rng() in the reference's order: origin = float(uniform3(-1, 1) * 0.5 L.x) (z = 0 in 2D), then the Fisher-Yates order
+ * of the 8 (4 in 2D) subgrids, entry g standing for the offset (g & 1, g >> 1 & 1, g >> 2 & 1).  The handle owns the cell list, the
+ * sorted unshifted positions and two counters per cell.  One step, all on `stream`, no host synchronisation:
+ *   list of d_pos + origin on cellDim (as given: no <= 3-cells collapse);  sortPos = list.sortPos + (-origin);
+ *   per subgrid in subgridOrder, per non-empty cell of it with Saru(seed, step, icell), triesPerCell times:
+ *     tried[icell]++;  i = min(int(f() * nincell), nincell - 1);  new = old + jumpSize * (2 f() - 1) per axis (three draws; z kept in 2D);
+ *     getCell(new + origin) != cell: next try without another draw;  dH = sum_j u(new, j) - sum_j u(old, j) over the 27 (9) cells with
+ *     u the LJ pair energy of the table (0 at r2 == 0, the moved particle standing for itself);  accept if f() <= min(1, exp(-beta dH)):
+ *     sortPos[i] = new, accepted[icell]++
+ *   d_pos[groupIndex[k]] = sortPos[k]     (a particle that did not move ends at (p + o) - o in float)
+ * u is the whole pair energy, 2 x the per-particle half that the traversals accumulate.  Positions move by plain
+ * float multiply and add (no contraction).  No atomics: each kernel is deterministic (the same state gives the same bits run to run).  The
+ * two kernels sum dH in different orders, so a try within rounding of its threshold can be decided differently by one and the other.  cellDim: every extent
+ * even, x and y >= 4, z == 1 (2D) or >= 4; numberSubgrids 4 for z == 1, else 8; -1 otherwise and on null arguments.  Cells past the edge
+ * of a non-periodic axis are skipped.  Tunables (uammd_hip_set_tunable): "mc_baseline" = 1 runs the reference-shaped kernel (thread per
+ * cell, global memory) instead of the wave-per-cell kernel with the neighbourhood staged in LDS; "mc_stage_capacity" = rows of LDS per
+ * wave (default 512, at most 960): a cell whose neighbourhood holds more is walked in global memory by the same wave.
+ *
+ * uammd_mc_anderson_counters: the sums of tried and accepted over the cells since the last reset (synchronises the stream); reset != 0
+ * zeroes them behind the read.  uammd_mc_anderson_cell_counters: the per-cell values into host arrays of cellDim.x * y * z (tests).
+ * uammd_mc_anderson_energy (Anderson::sumEnergy, Anderson.cu:377-400): rebuilds the list on d_pos with origin 0 and writes the
+ * per-particle LJ energy (half of every pair, as uammd_lj_transverse_celllist) into d_energy[N], zeroed first. */
+typedef struct uammd_mc_anderson uammd_mc_anderson;
+int uammd_mc_anderson_create(uammd_mc_anderson **out);
+int uammd_mc_anderson_destroy(uammd_mc_anderson *h);
+int uammd_mc_anderson_step(uammd_mc_anderson *h, float *d_pos /*real4[N], updated*/, int numberParticles, const float boxL[3],
+                           const int boxPeriodic[3], const int cellDim[3], const float origin[3], const int *subgridOrder /*host*/,
+                           int numberSubgrids /*8 or 4*/, int triesPerCell, float beta, float jumpSize, unsigned int step,
+                           unsigned int seed, const uammd_lj_pair_parameters *d_paramTable, int ntypes, void *stream);
+int uammd_mc_anderson_counters(uammd_mc_anderson *h, unsigned long long *tried, unsigned long long *accepted, int reset, void *stream);
+int uammd_mc_anderson_cell_counters(uammd_mc_anderson *h, unsigned int *tried /*host, ncells*/, unsigned int *accepted, void *stream);
+int uammd_mc_anderson_energy(uammd_mc_anderson *h, const float *d_pos, int numberParticles, const float boxL[3],
+                             const int boxPeriodic[3], const int cellDim[3], const uammd_lj_pair_parameters *d_paramTable, int ntypes,
+                             float *d_energy, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Integrator kernels.  Replace

@@ -17,6 +17,7 @@ from .bdhi import BDHI, IBM, FCMKernels, Kernels, nextFFTWiseSize3D  # noqa: F40
 from .bonded import AngularBondedForces, BondedForces, BondedType, TorsionalBondedForces  # noqa: F401
 from .dpd import DPD, VerletNVE  # noqa: F401  (Potential.DPD is the same class)
 from .sph import SPH  # noqa: F401
+from .mc import MC_NVT  # noqa: F401
 
 __all__ = ["UammdHipError", "load", "Box", "ParticleData", "ParticleGroup", "CellList", "VerletList", "Potential", "PairForces", "Interactor",
-           "Integrator", "VerletNVT", "VerletNVE", "SPH", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream"]
+           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream"]

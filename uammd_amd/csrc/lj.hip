@@ -25,6 +25,7 @@
 
 namespace uammd_hip {
 int bonded_set_tunable(const char *name, int value);  // bonded.hip
+int mc_set_tunable(const char *name, int value);      // mc.hip
 
 // ---- two-phase pair evaluation ---------------------------------------------------------------------
 // Only ~15 % of the candidate pairs of a 27-cell walk are inside the cut-off (4.19 rc^3 of 27 rc^3),
@@ -642,7 +643,7 @@ int uammd_lj_process_pair_parameters(float cutOff, float sigma, float epsilon, i
 }
 
 int uammd_hip_set_tunable(const char *name, int value) {
-  if (name && bonded_set_tunable(name, value) == 0) return 0;
+  if (name && (bonded_set_tunable(name, value) == 0 || mc_set_tunable(name, value) == 0)) return 0;
   set_last_error("uammd_hip_set_tunable: unknown tunable or bad value");
   return -1;
 }

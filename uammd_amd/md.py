@@ -57,6 +57,9 @@ class Xorshift128plus:
     def uniform(self, lo, hi):
         return lo + (float(self.next()) / float(0xFFFFFFFFFFFFFFFF)) * (hi - lo)
 
+    def uniform3(self, lo, hi):
+        return (self.uniform(lo, hi), self.uniform(lo, hi), self.uniform(lo, hi))
+
     _spare, _have_spare = 0.0, False   # (one spare for every generator of the process, as utils/utils.h:77-104 has it)
 
     def gaussian(self, mean, std):
