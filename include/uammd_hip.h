@@ -610,6 +610,47 @@ int uammd_icm_set_fluid_velocity(uammd_icm *h, const float *d_in, void *stream);
 int uammd_icm_set_noise(uammd_icm *h, const float *d_random); /* test hook: 6*ncells fluid random numbers, slot-major */
 
 /* ------------------------------------------------------------------------------------------------
+ * Hydro::ICM_Compressible — compressible Inertial Coupling Method, triply periodic.  Replaces
+ *   ICM_Compressible_impl<DefaultWalls> / forwardTime     Integrator/Hydro/ICM_Compressible.cuh:183-452, ICM_Compressible.cu:246-257
+ *   rungeKuttaSubStepD, momentumToVelocityD, fillStochasticTensorD, spreadParticleForces, interpolateFluidVelocities
+ *                                                         ICM_Compressible/{FluidSolver,SpatialDiscretization,Fluctuations,spreadInterp}.cuh
+ * Density, momentum and velocity persist in the handle between steps: n^3 floats each, x fastest, no ghost cells, momentum and
+ * velocity on the faces (component a of cell i at r_i + h_a/2).  Exactly one of hydrodynamicRadius > 0 / cells[0] > 0; the
+ * reference's parameter checks fail with its messages.  seed is used as given (the callers draw one when theirs is 0).
+ * Precondition: CUBIC cells (boxSize[a] / cells[a] the same on the three axes).  As in the reference, the window's scale is 1 / h_x on
+ * every axis and the Laplacian and grad div are sums of differences over h_b divided by h_a; other cells are accepted and run, but
+ * what they compute is not the continuum operator.
+ * Rounding: the Runge-Kutta combination A U^a + B (U^b + dU) is evaluated as U^a + B ((U^b + dU) - U^a), so that an unchanged state
+ * is returned exactly; results differ from the reference's literal form at the level of an ulp per sub-stage.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_icmc uammd_icmc;
+typedef struct {
+  float boxSize[3];
+  int cells[3];
+  float shearViscosity, bulkViscosity, speedOfSound, temperature, dt, hydrodynamicRadius;
+  unsigned int seed;
+} uammd_icmc_parameters;
+/* the parameter checks alone (host code, no GPU): 0, or -2 with the reference's message in uammd_hip_last_error() */
+int uammd_icmc_validate(const uammd_icmc_parameters *par);
+int uammd_icmc_create(const uammd_icmc_parameters *par, uammd_icmc **out, int cells[3]); /* validates; the fluid starts at rho = 1, v = 0 */
+int uammd_icmc_destroy(uammd_icmc *h);
+/* n^3 floats each (NULL: that field keeps its values); the momentum is derived: g_a = v_a (rho_i + rho_{i+a}) / 2 */
+int uammd_icmc_set_fluid(uammd_icmc *h, const float *d_density, const float *d_vx, const float *d_vy, const float *d_vz, void *stream);
+/* the staggered fields; null pointers (the arrays or their entries) are skipped */
+int uammd_icmc_get_fluid(uammd_icmc *h, float *d_density, float *const d_v[3], float *const d_g[3], void *stream);
+/* the velocity averaged to the cell centres (computeCollocatedVelocityD, SpatialDiscretization.cuh:419-444) */
+int uammd_icmc_get_collocated_velocity(uammd_icmc *h, float *d_vx, float *d_vy, float *d_vz, void *stream);
+/* One step = predictor (d_pos real4[N]: q^n -> q^{n+1/2}, q^n kept in the handle), the caller's Interactors at q^{n+1/2}, then the
+ * forcing, the noise, the three Runge-Kutta sub-stages and the corrector (d_pos -> q^{n+1}); d_force real4[N] or NULL.  N = 0: fluid only.
+ * The second call counts the step (the noise of step s is Saru(seed, s, cell), s from 0). */
+int uammd_icmc_predictor(uammd_icmc *h, float *d_pos, int numberParticles, void *stream);
+int uammd_icmc_fluid_and_corrector(uammd_icmc *h, float *d_pos, const float *d_force, int numberParticles, void *stream);
+/* Test hooks: the stochastic stress as float2 W[6][ncells] = {W_A, W_B} of the entries xx, yy, zz, xy, xz, yz (12 ncells floats).
+ * get: the numbers the handle draws at `step`.  set: the following steps use a copy of d_noise instead of drawing (NULL: draw again). */
+int uammd_icmc_get_noise(uammd_icmc *h, unsigned int step, float *d_out, void *stream);
+int uammd_icmc_set_noise(uammd_icmc *h, const float *d_noise, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Triply periodic electrostatics (another consumer of the spread / FFT / gather engine).  Replaces
  *   Poisson::Poisson / sum / computeFieldPotentialAtParticles    Interactor/SpectralEwaldPoisson.cuh:83-136, .cu:71-160
  *   farField (spread q, R2C, chargeFourier2FieldAndPotential, 4 x C2R, gather + UnZip2Real4)   .cu:332-360, :410-559

@@ -47,6 +47,12 @@ class ICMParameters(C.Structure):
                 ("removeTotalMomentum", C.c_int), ("seed", C.c_uint)]
 
 
+class ICMCompressibleParameters(C.Structure):
+    _fields_ = [("boxSize", C.c_float * 3), ("cells", C.c_int * 3), ("shearViscosity", C.c_float), ("bulkViscosity", C.c_float),
+                ("speedOfSound", C.c_float), ("temperature", C.c_float), ("dt", C.c_float), ("hydrodynamicRadius", C.c_float),
+                ("seed", C.c_uint)]
+
+
 class FIBParameters(C.Structure):
     _fields_ = [("boxSize", C.c_float * 3), ("temperature", C.c_float), ("viscosity", C.c_float), ("hydrodynamicRadius", C.c_float),
                 ("dt", C.c_float), ("cells", C.c_int * 3), ("scheme", C.c_int), ("seed", C.c_uint)]
@@ -228,6 +234,16 @@ SIGNATURES = {
     "uammd_icm_get_fluid_velocity": (_i, [_vp, _vp, _i, _vp]),
     "uammd_icm_set_fluid_velocity": (_i, [_vp, _vp, _vp]),
     "uammd_icm_set_noise": (_i, [_vp, _vp]),
+    "uammd_icmc_validate": (_i, [C.POINTER(ICMCompressibleParameters)]),
+    "uammd_icmc_create": (_i, [C.POINTER(ICMCompressibleParameters), C.POINTER(_vp), C.POINTER(_i3)]),
+    "uammd_icmc_destroy": (_i, [_vp]),
+    "uammd_icmc_set_fluid": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "uammd_icmc_get_fluid": (_i, [_vp, _vp, C.POINTER(_vp * 3), C.POINTER(_vp * 3), _vp]),
+    "uammd_icmc_get_collocated_velocity": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "uammd_icmc_predictor": (_i, [_vp, _vp, _i, _vp]),
+    "uammd_icmc_fluid_and_corrector": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_icmc_get_noise": (_i, [_vp, _u, _vp, _vp]),
+    "uammd_icmc_set_noise": (_i, [_vp, _vp, _vp]),
     "uammd_fib_create": (_i, [C.POINTER(FIBParameters), C.POINTER(_vp), C.POINTER(_i3), C.POINTER(_f)]),
     "uammd_fib_destroy": (_i, [_vp]),
     "uammd_fib_forward": (_i, [_vp, _vp, _vp, _i, _vp]),
