@@ -1066,6 +1066,55 @@ int uammd_bonded_sum(uammd_bonded *h, const float *d_pos, float *d_force, float 
 /* the CSR as laid out: rows, entries and how many rows each shape takes under the current "bonded_wave_threshold" */
 int uammd_bonded_get_shape(uammd_bonded *h, int *rows, int *entries, int *laneRows, int *waveRows);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fast Chebyshev and Fourier-Chebyshev transforms (chebyshev.hip).  Replaces
+ *   chebyshevTransform3DCufft / inverseChebyshevTransform3DCufft / fourierChebyshevTransform3DCufft /
+ *   inverseFourierChebyshevTransform3DCufft            misc/Chebyshev/FastChebyshevTransform.cuh:147-260
+ * A field holds nx ny nz complex values, element (i, j, k) at i + nx (j + ny k); plane k lies at cos(pi k / (nz - 1)).  With n = nz - 1:
+ *   forward  c_k = pm_k / (2 n) [f_0 + (-1)^k f_n + 2 sum_{j = 1}^{n - 1} f_j cos(pi j k / n)],  pm_k = 1 for k = 0 and k = n, else 2
+ *   inverse  f_j = sum_k c_k cos(pi j k / n)
+ * The Fourier-Chebyshev calls add a 2-D complex transform over (i, j) in every plane: forward divided by nx ny, inverse not.
+ * Out of place: d_in == d_out, a null pointer and nz < 2 are errors with a message.  The handle keeps the cosine table and the plans.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_fct uammd_fct;
+#define UAMMD_FCT_FORWARD 1
+#define UAMMD_FCT_INVERSE (-1)
+int uammd_fct_create(int nx, int ny, int nz, int double_precision, uammd_fct **out);
+int uammd_fct_destroy(uammd_fct *h);
+int uammd_fct_chebyshev(uammd_fct *h, const float *d_in, float *d_out, int direction, void *stream);
+int uammd_fct_chebyshev_f64(uammd_fct *h, const double *d_in, double *d_out, int direction, void *stream);
+int uammd_fct_fourier_chebyshev(uammd_fct *h, const float *d_in, float *d_out, int direction, void *stream);
+int uammd_fct_fourier_chebyshev_f64(uammd_fct *h, const double *d_in, double *d_out, int direction, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Batched boundary value problem solver (bvp.hip, bvp_host.hpp).  Replaces
+ *   BVP::BatchedBVPHandlerReal / BatchedBVPGPUSolverReal::solve       misc/BoundaryValueProblem/BVPSolver.cuh:161-290
+ * y'' - k^2 y = f on [-H, H] in Chebyshev space, one system per wave number, with
+ *   tfi y'(H) / H + tsi y(H) / H^2 = alpha,   bfi y'(-H) / H + bsi y(-H) / H^2 = beta.
+ * create: k, tfi, tsi, bfi, bsi are HOST doubles [nsys]; the tables are computed in double precision and kept on the device in the
+ * precision asked for.  nz < 4, a non-finite k or factor and a singular 2 x 2 boundary system refuse the whole batch (the message names
+ * the system).
+ * solve: complex arrays (re, im interleaved).  Element i of system s of right-hand side r sits at r nsys nz + s sysStride + i coefStride,
+ * with (sysStride, coefStride) = (1, nsys) - the solvers' layout - or (nz, 1); d_alpha / d_beta hold nrhs nsys values.  d_fn is not
+ * modified; d_an receives the coefficients of y'', d_cn those of y.  A system's result depends on neither its place in the batch nor
+ * the batch's size.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_bvp uammd_bvp;
+int uammd_bvp_create(int nsys, int nz, double H, const double *k, const double *tfi, const double *tsi, const double *bfi,
+                     const double *bsi, int double_precision, uammd_bvp **out);
+int uammd_bvp_destroy(uammd_bvp *h);
+int uammd_bvp_solve(uammd_bvp *h, const float *d_fn, const float *d_alpha, const float *d_beta, float *d_an, float *d_cn, int nrhs,
+                    long long sysStride, long long coefStride, void *stream);
+int uammd_bvp_solve_f64(uammd_bvp *h, const double *d_fn, const double *d_alpha, const double *d_beta, double *d_an, double *d_cn, int nrhs,
+                        long long sysStride, long long coefStride, void *stream);
+/* The device tables, for kernels of the caller's own (include/uammd/device/BVP.hip.hpp lays Tables<U> over them): rows of nsys
+ * values, element s of row i at s + nsys i - beta[nz], diagonal_p2[nz], diagonal_m2[nz], C A^-1 [2 nz], 2 x 2 matrix [4], k^2 H^2 [1]. */
+typedef struct {
+  const void *d_tables; /* float or double, as the handle was created */
+  int nsys, nz, double_precision;
+} uammd_bvp_tables;
+int uammd_bvp_device_tables(uammd_bvp *h, uammd_bvp_tables *out);
+
 #ifdef __cplusplus
 }
 #endif

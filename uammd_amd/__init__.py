@@ -18,6 +18,9 @@ from .bonded import AngularBondedForces, BondedForces, BondedType, TorsionalBond
 from .dpd import DPD, VerletNVE  # noqa: F401  (Potential.DPD is the same class)
 from .sph import SPH  # noqa: F401
 from .mc import MC_NVT  # noqa: F401
+from .chebyshev import FastChebyshevTransform  # noqa: F401
+from .bvp import BatchedBVP  # noqa: F401
 
 __all__ = ["UammdHipError", "load", "Box", "ParticleData", "ParticleGroup", "CellList", "VerletList", "Potential", "PairForces", "Interactor",
-           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream"]
+           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream",
+           "FastChebyshevTransform", "BatchedBVP"]

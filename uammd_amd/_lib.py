@@ -96,6 +96,10 @@ class FCMParameters64(C.Structure):
     _fields_ = [("boxSize", C.c_double * 3), ("cells", C.c_int * 3), ("viscosity", C.c_double), ("kernel", IBMKernel64)]
 
 
+class BVPTables(C.Structure):
+    _fields_ = [("d_tables", C.c_void_p), ("nsys", C.c_int), ("nz", C.c_int), ("double_precision", C.c_int)]
+
+
 _f3 = C.c_float * 3
 _i3 = C.c_int * 3
 _vp = C.c_void_p
@@ -145,6 +149,17 @@ SIGNATURES = {
     "uammd_bonded_refresh": (_i, [_vp, _vp, _i, _vp]),
     "uammd_bonded_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "uammd_bonded_get_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "uammd_fct_create": (_i, [_i, _i, _i, _i, C.POINTER(_vp)]),
+    "uammd_fct_destroy": (_i, [_vp]),
+    "uammd_fct_chebyshev": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_fct_chebyshev_f64": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_fct_fourier_chebyshev": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_fct_fourier_chebyshev_f64": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_bvp_create": (_i, [_i, _i, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _i, C.POINTER(_vp)]),
+    "uammd_bvp_destroy": (_i, [_vp]),
+    "uammd_bvp_solve": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp]),
+    "uammd_bvp_solve_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp]),
+    "uammd_bvp_device_tables": (_i, [_vp, C.POINTER(BVPTables)]),
     "uammd_celllist_create": (_i, [C.POINTER(_vp)]),
     "uammd_celllist_destroy": (_i, [_vp]),
     "uammd_celllist_create_grid": (_i, [_f3, _i3, _f3, _i3, _f3, _i3]),

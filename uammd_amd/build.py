@@ -15,7 +15,8 @@ def _stale():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [
-        os.path.join(_HERE, "..", "include", "uammd_hip.h")]
+        os.path.join(_HERE, "..", "include", "uammd_hip.h"),
+        os.path.join(_HERE, "..", "include", "uammd", "device", "BVP.hip.hpp")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.isfile(d))
 
 
