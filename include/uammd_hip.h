@@ -1115,6 +1115,65 @@ typedef struct {
 } uammd_bvp_tables;
 int uammd_bvp_device_tables(uammd_bvp *h, uammd_bvp_tables *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Doubly periodic electrostatics in a slab (dppoisson.hip).  Replaces
+ *   DPPoissonSlab                          Interactor/DoublyPeriodic/DPPoissonSlab.cuh, PoissonSlab/...
+ * Charges of Gaussian width gw between two walls at z = +-H/2, periodic in x and y.  permitivity = (top, bottom, inside); an infinite
+ * wall permittivity is a metallic wall, whose surface value is a potential instead of a charge density.  Exactly one of split and Nxy
+ * is positive.  create refuses what the reference's constructor refuses, with its message, before anything touches the device; with
+ * out == NULL it only fills info (host only: no device is needed).
+ * A particle with |z| > H/2 is left out of every stage, receives nothing and is counted (uammd_dppoisson_outside_count).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_dppoisson uammd_dppoisson;
+typedef struct {
+  double Lxy[2], H, gw, split;
+  int Nxy;
+  double permitivity[3]; /* top, bottom, inside */
+  double tolerance, upsampling;
+  int support;
+  double numberStandardDeviations;
+} uammd_dppoisson_parameters;
+typedef struct {
+  int cells[3];
+  double He, gt, h;
+  int support, supportZ; /* nodes per periodic axis; the reference's bound on the planes a window reaches (spreadInterp.cuh:33-35) */
+  double nearFieldCutOff;
+  int nTable;
+  double kmax, split;
+} uammd_dppoisson_info;
+int uammd_dppoisson_create(const uammd_dppoisson_parameters *par, int double_precision, uammd_dppoisson **out, uammd_dppoisson_info *info);
+int uammd_dppoisson_destroy(uammd_dppoisson *h);
+/* "simple_spread": a lane per particle with atomic adds instead of the owner-computes spread (cross-check); "keep_stages": keep the
+ * spread grid for uammd_dppoisson_get_stage; "skip_near_field": far field only (timing); "time_stages": record device events between
+ * the stage launches for uammd_dppoisson_stage_times.  The window takes at most 16 nodes per axis (support <= 16; the reference has no
+ * such limit): the gather keeps ceil(support^2 / 64) <= 4 columns per lane in registers; a larger support is refused by create. */
+int uammd_dppoisson_set_option(uammd_dppoisson *h, const char *name, int value);
+/* HOST arrays of nx ny samples at x = (i / nx - 1/2) Lx, y = (j / ny - 1/2) Ly, element (i, j) at i + nx j; NULL means zeros */
+int uammd_dppoisson_set_surface_values(uammd_dppoisson *h, const double *top, const double *bottom);
+/* setSurfaceValuesZeroModeFourier: a uniform wall value per wall (the other modes keep their values) */
+int uammd_dppoisson_set_surface_zero_mode(uammd_dppoisson *h, double top, double bottom);
+/* Interactor::sum: far field, then near field; force real4[N] += q E (w untouched), energy[N] += q phi, always both.  virial != 0 is
+ * refused ("not implemented").  N = 0 launches nothing. */
+int uammd_dppoisson_sum(uammd_dppoisson *h, const float *d_pos, const float *d_charge, int numberParticles, float *d_force, float *d_energy,
+                        int virial, void *stream);
+int uammd_dppoisson_sum_f64(uammd_dppoisson *h, const double *d_pos, const double *d_charge, int numberParticles, double *d_force, double *d_energy,
+                            int virial, void *stream);
+/* computeFieldPotentialAtParticles: d_fieldPotential real4[N] += (Ex, Ey, Ez, phi); like the reference's call it adds to force and energy too */
+int uammd_dppoisson_field_potential(uammd_dppoisson *h, const float *d_pos, const float *d_charge, int numberParticles, float *d_fieldPotential,
+                                    float *d_force, float *d_energy, void *stream);
+int uammd_dppoisson_field_potential_f64(uammd_dppoisson *h, const double *d_pos, const double *d_charge, int numberParticles,
+                                        double *d_fieldPotential, double *d_force, double *d_energy, void *stream);
+/* the corrected k = 0 column of the last call: nz x (Ex, Ey, Ez, phi) complex as 8 nz HOST doubles (synchronises) */
+int uammd_dppoisson_get_k0_mode(uammd_dppoisson *h, double *out);
+int uammd_dppoisson_outside_count(uammd_dppoisson *h, int *count); /* synchronises */
+/* test hook, into DEVICE memory in the handle's precision: "grid_near", "grid_all" (nx ny nz reals; option keep_stages) and "mismatch"
+ * (4 nx ny + 2 complex: mP0, mPH, mE0, mEH, component c of wave number s = i + nx j at c nx ny + s, then the k = 0 line A0, B0) */
+int uammd_dppoisson_get_stage(uammd_dppoisson *h, const char *name, void *d_out);
+/* Milliseconds per stage of the last run (option time_stages; synchronises), ms[13]: classify, spread, forward transform, solve (both
+ * systems, both at the walls, the mismatch: one kernel), correction, z pass of d phi / dz, z pass of phi, assemble, inverse transform of
+ * (Ex, Ey), of (Ez, phi), gather, cell list + pack, near field; 0 for a stage that did not run */
+int uammd_dppoisson_stage_times(uammd_dppoisson *h, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ streams and torch.distributed.  There is no CPU fallback anywhere in this packag
 from ._lib import UammdHipError, load  # noqa: F401
 from .md import (BD, Box, CellList, Integrator, Interactor, PairForces, ParticleData, ParticleGroup, Potential,  # noqa: F401
                  VerletList, VerletNVT, current_stream)
-from .electrostatics import Poisson  # noqa: F401
+from .electrostatics import DPPoissonSlab, Poisson  # noqa: F401
 from .hydro import Hydro  # noqa: F401
 from .checkpoint import restoreParticleData, saveParticleData  # noqa: F401
 from .bdhi import BDHI, IBM, FCMKernels, Kernels, nextFFTWiseSize3D  # noqa: F401
@@ -22,5 +22,5 @@ from .chebyshev import FastChebyshevTransform  # noqa: F401
 from .bvp import BatchedBVP  # noqa: F401
 
 __all__ = ["UammdHipError", "load", "Box", "ParticleData", "ParticleGroup", "CellList", "VerletList", "Potential", "PairForces", "Interactor",
-           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "Kernels", "FCMKernels", "current_stream",
+           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "DPPoissonSlab", "Kernels", "FCMKernels", "current_stream",
            "FastChebyshevTransform", "BatchedBVP"]

@@ -100,6 +100,17 @@ class BVPTables(C.Structure):
     _fields_ = [("d_tables", C.c_void_p), ("nsys", C.c_int), ("nz", C.c_int), ("double_precision", C.c_int)]
 
 
+class DPPoissonParameters(C.Structure):
+    _fields_ = [("Lxy", C.c_double * 2), ("H", C.c_double), ("gw", C.c_double), ("split", C.c_double), ("Nxy", C.c_int),
+                ("permitivity", C.c_double * 3), ("tolerance", C.c_double), ("upsampling", C.c_double), ("support", C.c_int),
+                ("numberStandardDeviations", C.c_double)]
+
+
+class DPPoissonInfo(C.Structure):
+    _fields_ = [("cells", C.c_int * 3), ("He", C.c_double), ("gt", C.c_double), ("h", C.c_double), ("support", C.c_int),
+                ("supportZ", C.c_int), ("nearFieldCutOff", C.c_double), ("nTable", C.c_int), ("kmax", C.c_double), ("split", C.c_double)]
+
+
 _f3 = C.c_float * 3
 _i3 = C.c_int * 3
 _vp = C.c_void_p
@@ -160,6 +171,19 @@ SIGNATURES = {
     "uammd_bvp_solve": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp]),
     "uammd_bvp_solve_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp]),
     "uammd_bvp_device_tables": (_i, [_vp, C.POINTER(BVPTables)]),
+    "uammd_dppoisson_create": (_i, [C.POINTER(DPPoissonParameters), _i, C.POINTER(_vp), C.POINTER(DPPoissonInfo)]),
+    "uammd_dppoisson_destroy": (_i, [_vp]),
+    "uammd_dppoisson_set_option": (_i, [_vp, C.c_char_p, _i]),
+    "uammd_dppoisson_set_surface_values": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "uammd_dppoisson_set_surface_zero_mode": (_i, [_vp, _d, _d]),
+    "uammd_dppoisson_sum": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "uammd_dppoisson_sum_f64": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "uammd_dppoisson_field_potential": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "uammd_dppoisson_field_potential_f64": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "uammd_dppoisson_get_k0_mode": (_i, [_vp, C.POINTER(_d)]),
+    "uammd_dppoisson_outside_count": (_i, [_vp, C.POINTER(_i)]),
+    "uammd_dppoisson_get_stage": (_i, [_vp, C.c_char_p, _vp]),
+    "uammd_dppoisson_stage_times": (_i, [_vp, C.POINTER(_d)]),
     "uammd_celllist_create": (_i, [C.POINTER(_vp)]),
     "uammd_celllist_destroy": (_i, [_vp]),
     "uammd_celllist_create_grid": (_i, [_f3, _i3, _f3, _i3, _f3, _i3]),

@@ -1,0 +1,60 @@
+// Indexing of a doubly periodic grid that is regular in x and y and Chebyshev in z (misc/ChevyshevUtils.cuh:72-175 in the reference),
+// with the truncated Gaussian window the doubly periodic solvers spread and gather with (PoissonSlab/spreadInterp.cuh:22-67) and the
+// footprint rule of the reference's immersed boundary kernels (misc/IBM.cu:10-31).  DESIGN.md 17.
+//   node (i, j) lies at ((i / nx - 1/2) Lx, (j / ny - 1/2) Ly): the reference's "cell centre" of this grid is the cell's corner
+//   plane k lies at (Htot / 2) cos(pi k / (nz - 1)), k = 0 at the top; the heights come from a table computed once on the host
+// A window covers `support` consecutive nodes per periodic axis, starting at leftmost(), and every plane within 1.000001 rmax.
+#pragma once
+#include "device_common.hpp"
+
+namespace uammd_hip {
+
+UH_HD float exp_(float a) { return expf(a); }
+UH_HD double exp_(double a) { return exp(a); }
+UH_HD float acos_(float a) { return acosf(a); }
+UH_HD double acos_(double a) { return acos(a); }
+UH_HD float abs_(float a) { return fabsf(a); }
+UH_HD double abs_(double a) { return fabs(a); }
+
+template <class U> struct ChebGrid {
+  int nx, ny, nz, support;
+  U Lx, Ly, Htot, hx, hy, invhx, invhy;
+  U prefactor, tau, rmax, rcut;  // window: prefactor exp(tau r^2) for |r| <= rcut = 1.000001 rmax, else 0
+  const U *zplane;               // [nz] plane heights (device)
+  const U *qw;                   // [nz] quadrature weights hx hy (Htot / 2) clencurt(k, nz - 1) (device)
+
+  UH_D U phi(U r) const { return abs_(r) > rcut ? U(0) : prefactor * exp_(tau * r * r); }
+  UH_D static U fold(U x, U L) { return x - floor_(x / L + U(0.5)) * L; }
+  // the cell of a folded coordinate, clamped: no input can produce an index outside [0, n)
+  UH_D static int cell(U xin, U L, U invh, int n) {
+    int c = (int)((xin + U(0.5) * L) * invh);
+    if (c == n) c = 0;
+    return c < 0 ? 0 : (c >= n ? n - 1 : c);
+  }
+  UH_D static U node_distance(U xin, int node, U L, U h) { return fold(xin - (U(-0.5) * L + h * U(node)), L); }
+  // first node of the window of a folded coordinate (may be negative: nodes wrap)
+  UH_D int leftmost(U xin, U L, U h, U invh, int n) const {
+    const int c = cell(xin, L, invh, n);
+    int P = support / 2;
+    if (abs_(node_distance(xin, c - P, L, h)) > U(support) * h / U(2.0)) P -= 1;
+    return c - P;
+  }
+  UH_D int leftmost_x(U xin) const { return leftmost(xin, Lx, hx, invhx, nx); }
+  UH_D int leftmost_y(U yin) const { return leftmost(yin, Ly, hy, invhy, ny); }
+  UH_D static int wrap(int c, int n) { return c < 0 ? c + n : (c >= n ? c - n : c); }
+  UH_D U weight_x(U xin, int node) const { return phi(node_distance(xin, node, Lx, hx)); }
+  UH_D U weight_y(U yin, int node) const { return phi(node_distance(yin, node, Ly, hy)); }
+  // planes [lo, hi] that can lie within rmax of z: the reference's range (spreadInterp.cuh:42-50) widened by one plane on each side and
+  // clamped; the window's own cut decides inside it
+  UH_D void plane_range(U z, int &lo, int &hi) const {
+    const U bound = Htot * U(0.5);
+    const U zt = fmin(z + rmax, bound), zb = fmax(z - rmax, -bound);
+    const U a = fmin(fmax(zt / bound, U(-1)), U(1)), b = fmin(fmax(zb / bound, U(-1)), U(1));
+    lo = (int)(U(nz - 1) * (acos_(a) / U(M_PI))) - 1;
+    hi = (int)(U(nz - 1) * (acos_(b) / U(M_PI))) + 1;
+    lo = lo < 0 ? 0 : (lo > nz - 1 ? nz - 1 : lo);
+    hi = hi < 0 ? 0 : (hi > nz - 1 ? nz - 1 : hi);
+  }
+};
+
+}  // namespace uammd_hip
