@@ -1174,6 +1174,85 @@ int uammd_dppoisson_get_stage(uammd_dppoisson *h, const char *name, void *d_out)
  * (Ex, Ey), of (Ez, phi), gather, cell list + pack, near field; 0 for a stage that did not run */
 int uammd_dppoisson_stage_times(uammd_dppoisson *h, double *ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Doubly periodic Stokes mobility and its integrator (dpstokes.hip).  Replaces
+ *   DPStokesSlab_ns::DPStokes, DPStokesIntegrator      Integrator/BDHI/DoublyPeriodic/DPStokesSlab.cuh, StokesSlab/...
+ * Particles in a fluid that is periodic in x and y and open (mode 0), bounded by a no-slip wall at z = -H/2 (1) or by walls at both
+ * z = +-H/2 (2).  The window is the Barnett-Magland one: w nodes per axis, width beta (beta[1], beta[2] < 0 take beta[0]), alpha the
+ * half support in cells.  nz < 0 takes pi H / min(hx, hy).  create refuses what the reference's constructor refuses, with its message,
+ * and nz < 4, a support above 16 nodes and a window without w, alpha, beta[0], before anything touches the device; with out == NULL it
+ * only fills info (host only: no device is needed).
+ * Positions and forces are rows of posStride / forceStride (3 or 4) reals; velocities are rows of 3.  A particle with |z| > H/2 or a
+ * non-finite coordinate is left out of every stage, receives zero and is counted (uammd_dpstokes_outside_count).  Torques are not
+ * implemented: a non-null d_torque is refused.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_dpstokes uammd_dpstokes;
+typedef struct uammd_dpstokes_integrator uammd_dpstokes_integrator;
+typedef struct {
+  int nx, ny, nz;
+  double viscosity, Lx, Ly, H;
+  double w, beta[3], alpha;
+  int mode; /* 0 none, 1 bottom, 2 slit */
+} uammd_dpstokes_parameters;
+typedef struct {
+  int cells[3], support;
+  double hx, hy, rmax, beta[3];
+} uammd_dpstokes_info;
+typedef struct {
+  double temperature, dt, tolerance; /* tolerance: of the Lanczos iteration */
+  double deltaRFD;                   /* <= 0: the reference's 1e-6 (double precision only: single precision refuses temperature > 0 without it) */
+  int useLeimkuhler;
+  unsigned int seed, seedRFD;
+} uammd_dpstokes_integrator_parameters;
+int uammd_dpstokes_create(const uammd_dpstokes_parameters *par, int double_precision, uammd_dpstokes **out, uammd_dpstokes_info *info);
+int uammd_dpstokes_destroy(uammd_dpstokes *h);
+/* "simple_spread": a lane per particle with atomic adds instead of the owner-computes spread (cross-check); "time_stages": record device
+ * events between the stage launches for uammd_dpstokes_stage_times */
+int uammd_dpstokes_set_option(uammd_dpstokes *h, const char *name, int value);
+/* DPStokes::Mdot: d_mf real3[N] = M F (overwritten) */
+int uammd_dpstokes_mdot(uammd_dpstokes *h, const float *d_pos, int posStride, const float *d_force, int forceStride, const float *d_torque,
+                        int numberParticles, float *d_mf, void *stream);
+int uammd_dpstokes_mdot_f64(uammd_dpstokes *h, const double *d_pos, int posStride, const double *d_force, int forceStride, const double *d_torque,
+                            int numberParticles, double *d_mf, void *stream);
+/* computeAverageVelocity: the plane average of u (direction 0) or v (1) at the nz planes, HOST doubles, plane 0 at the top (synchronises) */
+int uammd_dpstokes_average_velocity(uammd_dpstokes *h, const float *d_pos, int posStride, const float *d_force, int forceStride,
+                                    int numberParticles, int direction, double *averageVelocity, void *stream);
+int uammd_dpstokes_average_velocity_f64(uammd_dpstokes *h, const double *d_pos, int posStride, const double *d_force, int forceStride,
+                                        int numberParticles, int direction, double *averageVelocity, void *stream);
+/* the corrected Chebyshev-space (u, v, w, p) of the last call into DEVICE memory in the handle's precision: 4 nz nx ny complex,
+ * coefficient m of wave number s = i + nx j of component c at (c nz + m) nx ny + s; normalised like the library's forward transform, so
+ * the k = 0 column of a velocity is its plane average (synchronises) */
+int uammd_dpstokes_fluid_cheb(uammd_dpstokes *h, float *d_out);
+int uammd_dpstokes_fluid_cheb_f64(uammd_dpstokes *h, double *d_out);
+int uammd_dpstokes_outside_count(uammd_dpstokes *h, int *count); /* synchronises */
+/* Milliseconds per stage of the last run (option time_stages; synchronises), ms[13]: classify, spread, forward transform of (fx, fy), of
+ * fz, pressure solve, velocity solves, correction constants, correction at the planes, its z passes, zero mode + assemble, inverse
+ * transform of (u, v), of (w, p), gather; 0 for a stage that did not run */
+int uammd_dpstokes_stage_times(uammd_dpstokes *h, double *ms);
+/* DPStokesIntegrator: a solver of its own plus the Lanczos handle.  step is forwardTime after the interactors have summed their forces:
+ * pos += dt M F [+ dt sqrt(2 T / dt) M^(1/2) W (averaged with the previous step's under useLeimkuhler) + the thermal drift].
+ * thermal_drift: d_drift real3[N] = (T dt / delta) [M(q + delta W / 2) W - M(q - delta W / 2) W] for the caller's W (real3[N]);
+ * fluctuations: d_out real3[N] = M^(1/2) W for the caller's W.  _solver: the integrator's solver (owned by the integrator). */
+int uammd_dpstokes_integrator_create(const uammd_dpstokes_parameters *par, const uammd_dpstokes_integrator_parameters *ipar, int double_precision,
+                                     uammd_dpstokes_integrator **out);
+int uammd_dpstokes_integrator_destroy(uammd_dpstokes_integrator *h);
+uammd_dpstokes *uammd_dpstokes_integrator_solver(uammd_dpstokes_integrator *h);
+int uammd_dpstokes_integrator_step(uammd_dpstokes_integrator *h, float *d_pos, int posStride, const float *d_force, int forceStride,
+                                   int numberParticles, void *stream);
+int uammd_dpstokes_integrator_step_f64(uammd_dpstokes_integrator *h, double *d_pos, int posStride, const double *d_force, int forceStride,
+                                       int numberParticles, void *stream);
+/* test hook: what the last step added up, real3[N] into DEVICE memory in the handle's precision (synchronises): which = 0 M F,
+ * 1 the fluctuations, 2 the thermal drift, 3 the fluctuations of the step before (useLeimkuhler) */
+int uammd_dpstokes_integrator_last(uammd_dpstokes_integrator *h, int which, int numberParticles, void *d_out);
+int uammd_dpstokes_integrator_thermal_drift(uammd_dpstokes_integrator *h, const float *d_pos, int posStride, const float *d_w, int numberParticles,
+                                            float *d_drift, void *stream);
+int uammd_dpstokes_integrator_thermal_drift_f64(uammd_dpstokes_integrator *h, const double *d_pos, int posStride, const double *d_w,
+                                                int numberParticles, double *d_drift, void *stream);
+int uammd_dpstokes_integrator_fluctuations(uammd_dpstokes_integrator *h, const float *d_pos, int posStride, const float *d_w, int numberParticles,
+                                           float *d_out, void *stream);
+int uammd_dpstokes_integrator_fluctuations_f64(uammd_dpstokes_integrator *h, const double *d_pos, int posStride, const double *d_w,
+                                               int numberParticles, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

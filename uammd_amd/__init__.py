@@ -20,7 +20,8 @@ from .sph import SPH  # noqa: F401
 from .mc import MC_NVT  # noqa: F401
 from .chebyshev import FastChebyshevTransform  # noqa: F401
 from .bvp import BatchedBVP  # noqa: F401
+from .dpstokes import DPStokes, DPStokesIntegrator, WallMode  # noqa: F401
 
 __all__ = ["UammdHipError", "load", "Box", "ParticleData", "ParticleGroup", "CellList", "VerletList", "Potential", "PairForces", "Interactor",
            "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "DPPoissonSlab", "Kernels", "FCMKernels", "current_stream",
-           "FastChebyshevTransform", "BatchedBVP"]
+           "FastChebyshevTransform", "BatchedBVP", "DPStokes", "DPStokesIntegrator", "WallMode"]

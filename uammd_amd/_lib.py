@@ -106,6 +106,21 @@ class DPPoissonParameters(C.Structure):
                 ("numberStandardDeviations", C.c_double)]
 
 
+class DPStokesParameters(C.Structure):
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("viscosity", C.c_double), ("Lx", C.c_double), ("Ly", C.c_double),
+                ("H", C.c_double), ("w", C.c_double), ("beta", C.c_double * 3), ("alpha", C.c_double), ("mode", C.c_int)]
+
+
+class DPStokesInfo(C.Structure):
+    _fields_ = [("cells", C.c_int * 3), ("support", C.c_int), ("hx", C.c_double), ("hy", C.c_double), ("rmax", C.c_double),
+                ("beta", C.c_double * 3)]
+
+
+class DPStokesIntegratorParameters(C.Structure):
+    _fields_ = [("temperature", C.c_double), ("dt", C.c_double), ("tolerance", C.c_double), ("deltaRFD", C.c_double),
+                ("useLeimkuhler", C.c_int), ("seed", C.c_uint), ("seedRFD", C.c_uint)]
+
+
 class DPPoissonInfo(C.Structure):
     _fields_ = [("cells", C.c_int * 3), ("He", C.c_double), ("gt", C.c_double), ("h", C.c_double), ("support", C.c_int),
                 ("supportZ", C.c_int), ("nearFieldCutOff", C.c_double), ("nTable", C.c_int), ("kmax", C.c_double), ("split", C.c_double)]
@@ -184,6 +199,27 @@ SIGNATURES = {
     "uammd_dppoisson_outside_count": (_i, [_vp, C.POINTER(_i)]),
     "uammd_dppoisson_get_stage": (_i, [_vp, C.c_char_p, _vp]),
     "uammd_dppoisson_stage_times": (_i, [_vp, C.POINTER(_d)]),
+    "uammd_dpstokes_create": (_i, [C.POINTER(DPStokesParameters), _i, C.POINTER(_vp), C.POINTER(DPStokesInfo)]),
+    "uammd_dpstokes_destroy": (_i, [_vp]),
+    "uammd_dpstokes_set_option": (_i, [_vp, C.c_char_p, _i]),
+    "uammd_dpstokes_mdot": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "uammd_dpstokes_mdot_f64": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "uammd_dpstokes_average_velocity": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_d), _vp]),
+    "uammd_dpstokes_average_velocity_f64": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_d), _vp]),
+    "uammd_dpstokes_fluid_cheb": (_i, [_vp, _vp]),
+    "uammd_dpstokes_fluid_cheb_f64": (_i, [_vp, _vp]),
+    "uammd_dpstokes_outside_count": (_i, [_vp, C.POINTER(_i)]),
+    "uammd_dpstokes_stage_times": (_i, [_vp, C.POINTER(_d)]),
+    "uammd_dpstokes_integrator_create": (_i, [C.POINTER(DPStokesParameters), C.POINTER(DPStokesIntegratorParameters), _i, C.POINTER(_vp)]),
+    "uammd_dpstokes_integrator_destroy": (_i, [_vp]),
+    "uammd_dpstokes_integrator_solver": (_vp, [_vp]),
+    "uammd_dpstokes_integrator_last": (_i, [_vp, _i, _i, _vp]),
+    "uammd_dpstokes_integrator_step": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
+    "uammd_dpstokes_integrator_step_f64": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
+    "uammd_dpstokes_integrator_thermal_drift": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "uammd_dpstokes_integrator_thermal_drift_f64": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "uammd_dpstokes_integrator_fluctuations": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "uammd_dpstokes_integrator_fluctuations_f64": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "uammd_celllist_create": (_i, [C.POINTER(_vp)]),
     "uammd_celllist_destroy": (_i, [_vp]),
     "uammd_celllist_create_grid": (_i, [_f3, _i3, _f3, _i3, _f3, _i3]),

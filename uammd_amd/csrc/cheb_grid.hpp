@@ -57,4 +57,50 @@ template <class U> struct ChebGrid {
   }
 };
 
+// The same grid with the window of the doubly periodic Stokes solver (StokesSlab/spreadInterp.cuh:70-135): the "exponential of a
+// semicircle" of Barnett and Magland per axis, phi(r) = bm(r / a) / a with a = (hx, hy, min(hx, hy)), zero beyond |r| = alpha a; in z
+// the particle's image in the nearer wall is subtracted.  The slab is the whole grid: planes at (H / 2) cos(pi k / (nz - 1)).  DESIGN.md 18.
+template <class U> struct ChebGridBM {
+  int nx, ny, nz, support;
+  U Lx, Ly, H, hx, hy, invhx, invhy;
+  U alpha, az, betax, betay, betaz, invnormx, invnormy, invnormz;
+  U rmax;    // w max(hx, hy) / 2: the planes a window is looked for in
+  U reachz;  // 1.000001 alpha az: no plane farther than this from a particle takes anything from it
+  const U *zplane;  // [nz] plane heights (device)
+  const U *qw;      // [nz] quadrature weights hx hy (H / 2) clencurt(k, nz - 1) (device)
+
+  UH_D static U bm(U r, U a, U alpha, U beta, U invnorm) {  // IBM_kernels.cuh:83-112
+    const U z = (r / a) / alpha;
+    const U dz2 = U(1) - z * z;
+    if (dz2 < U(0)) return U(0);
+    return (exp_(beta * (sqrt_(dz2) - U(1))) * invnorm) / a;
+  }
+  UH_D int leftmost(U xin, U L, U h, U invh, int n) const {
+    const int c = ChebGrid<U>::cell(xin, L, invh, n);
+    int P = support / 2;
+    if (abs_(ChebGrid<U>::node_distance(xin, c - P, L, h)) > U(support) * h / U(2.0)) P -= 1;
+    return c - P;
+  }
+  UH_D int leftmost_x(U xin) const { return leftmost(xin, Lx, hx, invhx, nx); }
+  UH_D int leftmost_y(U yin) const { return leftmost(yin, Ly, hy, invhy, ny); }
+  UH_D U weight_x(U xin, int node) const { return bm(ChebGrid<U>::node_distance(xin, node, Lx, hx), hx, alpha, betax, invnormx); }
+  UH_D U weight_y(U yin, int node) const { return bm(ChebGrid<U>::node_distance(yin, node, Ly, hy), hy, alpha, betay, invnormy); }
+  UH_D U weight_z(U z, U zk) const {
+    const U r = z - zk;
+    const U top = H - U(2.0) * z + r, bot = -H - U(2.0) * z + r;
+    const U rimg = fmin(abs_(top), abs_(bot));
+    return bm(r, az, alpha, betaz, invnormz) - bm(rimg, az, alpha, betaz, invnormz);
+  }
+  // planes [lo, hi] that can lie within rmax of z (spreadInterp.cuh:102-110), widened by one plane on each side and clamped
+  UH_D void plane_range(U z, int &lo, int &hi) const {
+    const U bound = H * U(0.5);
+    const U zt = fmin(z + rmax, bound), zb = fmax(z - rmax, -bound);
+    const U a = fmin(fmax(zt / bound, U(-1)), U(1)), b = fmin(fmax(zb / bound, U(-1)), U(1));
+    lo = (int)(U(nz - 1) * (acos_(a) / U(M_PI))) - 1;
+    hi = (int)(U(nz - 1) * (acos_(b) / U(M_PI))) + 1;
+    lo = lo < 0 ? 0 : (lo > nz - 1 ? nz - 1 : lo);
+    hi = hi < 0 ? 0 : (hi > nz - 1 ? nz - 1 : hi);
+  }
+};
+
 }  // namespace uammd_hip
