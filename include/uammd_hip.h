@@ -317,6 +317,39 @@ int uammd_mc_anderson_energy(uammd_mc_anderson *h, const float *d_pos, int numbe
                              const int boxPeriodic[3], const int cellDim[3], const uammd_lj_pair_parameters *d_paramTable, int ntypes,
                              float *d_energy, void *stream);
 
+/* Force biased Monte Carlo (Integrator/MonteCarlo/ForceBiased.cuh): the Metropolized Euler-Maruyama scheme (MALA), the integrator's own
+ * part of a trial; forces and per-particle energies come from the caller's interactors.  Single precision arrays,
+ * every sum and the acceptance exponent in double.  The handle owns the stored configuration X, F(X) (real4[N]) and E_X, the per-block
+ * partial sums and the result record (device, mirrored in pinned host memory).
+ *
+ * uammd_mc_forcebiased_begin: adopts d_pos, d_force as X, F(X) and E_X = sum_i d_energy[i] (the reference's firstStep after its
+ *   interactors ran).  An energy that is not finite, or past FLT_MAX, becomes FLT_MAX (here and in decide).
+ * uammd_mc_forcebiased_propose: one kernel reading the STORED arrays (a rejected trial needs no restore before the next proposal): per
+ *   particle i, rng = Saru(seed, step, i), xi.xy = rng.gf(0, 1), xi.z = rng.gf(0, 1).x; in float, without contraction,
+ *     d_pos[i].c = X[i].c + (F[i].c * stepSize + amp * xi.c),  amp = (float)sqrt(2.0 * stepSize / beta),  d_pos[i].w = X[i].w
+ *   d_noise, when not null, receives (xi.x, xi.y, xi.z, 0) per particle (test hook).
+ * uammd_mc_forcebiased_decide: after the caller has zeroed force and energy and run its interactors on Y = d_pos.  With h = stepSize:
+ *     E_Y = sum energy[i],  T_XY = sum |Y - X - h F(X)|^2 / (4 h),  T_YX = sum |X - Y - h F(Y)|^2 / (4 h)   (terms and sums in double)
+ *     exponent = -beta ((E_Y - E_X) + (T_YX - T_XY)),  accepted = Z < exp(exponent)   (a NaN exponent rejects)
+ *   accepted: stored <- (d_pos, d_force), E_X <- E_Y;  rejected: (d_pos, d_force) <- stored.  Two kernels, no atomics, no synchronisation:
+ *   the same inputs give the same bits on every run.
+ * uammd_mc_forcebiased_result: the one host synchronisation of a trial: the decision of the last decide (1 after begin) and
+ *   out = {E_X before, E_Y, T_XY, T_YX, exponent, current energy}.
+ * uammd_mc_forcebiased_stored: copies the stored X, F(X) into device arrays (test hook).
+ * Null arguments, numberParticles <= 0 or other than what begin adopted, stepSize <= 0 and beta < 0 return -1 with a message, decided on
+ * the host before anything touches the device. */
+typedef struct uammd_mc_forcebiased uammd_mc_forcebiased;
+int uammd_mc_forcebiased_create(uammd_mc_forcebiased **out);
+int uammd_mc_forcebiased_destroy(uammd_mc_forcebiased *h);
+int uammd_mc_forcebiased_begin(uammd_mc_forcebiased *h, const float *d_pos /*real4[N]*/, const float *d_force /*real4[N]*/,
+                               const float *d_energy /*real[N]*/, int numberParticles, void *stream);
+int uammd_mc_forcebiased_propose(uammd_mc_forcebiased *h, float *d_pos /*real4[N], written*/, int numberParticles, float stepSize, float beta,
+                                 unsigned int step, unsigned int seed, float *d_noise /*nullable, real4[N]*/, void *stream);
+int uammd_mc_forcebiased_decide(uammd_mc_forcebiased *h, float *d_pos, float *d_force, const float *d_energy, int numberParticles,
+                                float stepSize, float beta, double Z, void *stream);
+int uammd_mc_forcebiased_result(uammd_mc_forcebiased *h, int *accepted, double out[6], void *stream);
+int uammd_mc_forcebiased_stored(uammd_mc_forcebiased *h, float *d_pos_out, float *d_force_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Integrator kernels.  Replace
  *   VerletNVT::GronbechJensen_ns::integrateGPU<step>   Integrator/VerletNVT/GronbechJensen.cu:28-62

@@ -17,11 +17,11 @@ from .bdhi import BDHI, IBM, FCMKernels, Kernels, nextFFTWiseSize3D  # noqa: F40
 from .bonded import AngularBondedForces, BondedForces, BondedType, TorsionalBondedForces  # noqa: F401
 from .dpd import DPD, VerletNVE  # noqa: F401  (Potential.DPD is the same class)
 from .sph import SPH  # noqa: F401
-from .mc import MC_NVT  # noqa: F401
+from .mc import MC, MC_NVT  # noqa: F401
 from .chebyshev import FastChebyshevTransform  # noqa: F401
 from .bvp import BatchedBVP  # noqa: F401
 from .dpstokes import DPStokes, DPStokesIntegrator, WallMode  # noqa: F401
 
 __all__ = ["UammdHipError", "load", "Box", "ParticleData", "ParticleGroup", "CellList", "VerletList", "Potential", "PairForces", "Interactor",
-           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "BD", "BDHI", "IBM", "Poisson", "DPPoissonSlab", "Kernels", "FCMKernels", "current_stream",
+           "Integrator", "VerletNVT", "VerletNVE", "SPH", "MC_NVT", "MC", "BD", "BDHI", "IBM", "Poisson", "DPPoissonSlab", "Kernels", "FCMKernels", "current_stream",
            "FastChebyshevTransform", "BatchedBVP", "DPStokes", "DPStokesIntegrator", "WallMode"]

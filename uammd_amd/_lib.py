@@ -276,6 +276,13 @@ SIGNATURES = {
     "uammd_mc_anderson_counters": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _i, _vp]),
     "uammd_mc_anderson_cell_counters": (_i, [_vp, _vp, _vp, _vp]),
     "uammd_mc_anderson_energy": (_i, [_vp, _vp, _i, _f3, _i3, _i3, _vp, _i, _vp, _vp]),
+    "uammd_mc_forcebiased_create": (_i, [C.POINTER(_vp)]),
+    "uammd_mc_forcebiased_destroy": (_i, [_vp]),
+    "uammd_mc_forcebiased_begin": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "uammd_mc_forcebiased_propose": (_i, [_vp, _vp, _i, _f, _f, _u, _u, _vp, _vp]),
+    "uammd_mc_forcebiased_decide": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _d, _vp]),
+    "uammd_mc_forcebiased_result": (_i, [_vp, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "uammd_mc_forcebiased_stored": (_i, [_vp, _vp, _vp, _vp]),
     "uammd_verletnvt_gj": (_i, [_i, _vp, _vp, _vp, _vp, _f, _vp, _i, _f, _f, _i, _f, _u, _u, _vp]),
     "uammd_verletnvt_gj_keyed": (_i, [_i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _f, _f, _i, _f, _u, _u, _vp]),
     "uammd_verletnvt_gj_lj_step": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _f3, _i3, _f3, _i3, _i3, _vp, _i, _f, _f, _i, _f, _u, _u, _i, _vp]),
