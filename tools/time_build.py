@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Cell-list build timing on a melted C3-like configuration; checks the build variants against each other.
-usage: python tools/time_build.py [N]"""
+usage: [MELT=steps] [SINCE_SORT=steps] [UAMMD_HIP_LIB=another build] python tools/time_build.py [N]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -22,7 +22,7 @@ pd.hintSortByHash(box, [2.5] * 3)
 for _ in range(int(os.environ.get("MELT", "300"))):
     integ.forwardTime()
 pd.sortParticles()
-for _ in range(100):   # the bench's steady state: up to 500 steps since the last sort
+for _ in range(int(os.environ.get("SINCE_SORT", "100"))):   # the bench's steady state: up to 500 steps since the last sort
     integ.forwardTime()
 pos = pd.getPos("read")
 cd, ubox = hip.CellList.create_update_grid(box, [2.5] * 3)

@@ -14,9 +14,9 @@
 //                 is a provisional, order-nondeterministic rank inside the key);
 //   scan        : exclusive scan of the histogram (<= 2^maxbit entries, L2 resident) -> keyStart[];
 //   rank+scatter: each particle re-derives its STABLE rank = #{same-key particles with a smaller
-//                 original index} from the provisional per-key member list (~13 members, L2 hits),
-//                 then writes index/hash/sortPos at keyStart[key] + rank.  Deterministic, bit-equal
-//                 to the radix sort, ~3 streaming passes instead of ~8;
+//                 original index} from the provisional per-key member list (~13 members, read once
+//                 per workgroup into LDS), then writes index/hash/sortPos at the cell's first slot
+//                 + rank.  Deterministic, bit-equal to the radix sort, ~3 streaming passes instead of ~8;
 //   cell tables : cellStart/cellEnd come straight from keyStart (one thread per *cell*).
 // When the key space is too large for that (very sparse / huge grids) the build falls back to
 // rocPRIM's stable radix sort + a boundary-detection pass.
@@ -132,8 +132,6 @@ __global__ void __launch_bounds__(kBlock) k_hash_agg(float4 *__restrict__ pos, i
   constexpr int kSlotShift = 32 - (kAggPerThread == 4 ? 11 : kAggPerThread == 2 ? 10 : 9);
   static_assert(kAggSlots == (1 << (32 - kSlotShift)), "kSlotShift is log2 of the table size");
   __shared__ uint tKey[kAggSlots], tCnt[kAggSlots];
-  for (int s = threadIdx.x; s < kAggSlots; s += kBlock) { tKey[s] = 0xffffffffu; tCnt[s] = 0u; }
-  __syncthreads();
   const int base = blockIdx.x * (kBlock * kAggPerThread);
   uint myKey[kAggPerThread], mySlot[kAggPerThread], myRank[kAggPerThread];
   float4 p[kAggPerThread];
@@ -142,16 +140,20 @@ __global__ void __launch_bounds__(kBlock) k_hash_agg(float4 *__restrict__ pos, i
     const int i = base + u * kBlock + threadIdx.x;
     p[u] = (i < N) ? pos[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   }
+  float3 v[GJ1 ? kAggPerThread : 1];
+  float4 f4[GJ1 ? kAggPerThread : 1];
+  const int nRows = gj.nRows > 0 ? min(gj.nRows, N) : N;   // (rows beyond are ghosts: hashed, not integrated)
   if (GJ1) {
-    float3 v[kAggPerThread];
-    float4 f4[kAggPerThread];
-    const int nRows = gj.nRows > 0 ? min(gj.nRows, N) : N;   // (rows beyond are ghosts: hashed, not integrated)
 #pragma unroll
     for (int u = 0; u < kAggPerThread; ++u) {
       const int i = min(base + u * kBlock + (int)threadIdx.x, nRows - 1);
       v[u] = make_float3(gj.vel[3 * (size_t)i], gj.vel[3 * (size_t)i + 1], gj.vel[3 * (size_t)i + 2]);
       f4[u] = gj.force[i];
     }
+  }
+  // the table is cleared while those loads are in flight; the barrier that publishes it stands in front of the first insertion
+  for (int s = threadIdx.x; s < kAggSlots; s += kBlock) { tKey[s] = 0xffffffffu; tCnt[s] = 0u; }
+  if (GJ1) {
 #pragma unroll
     for (int u = 0; u < kAggPerThread; ++u) {
       const int i = base + u * kBlock + threadIdx.x;
@@ -189,6 +191,7 @@ __global__ void __launch_bounds__(kBlock) k_hash_agg(float4 *__restrict__ pos, i
       myKey[u] = h;
     }
   }
+  __syncthreads();
   bool first[kAggPerThread];
 #pragma unroll
   for (int u = 0; u < kAggPerThread; ++u) {
@@ -304,29 +307,56 @@ __global__ void __launch_bounds__(kBlock) k_key_scan(const uint *__restrict__ ke
   if (k1 == nKeys && k0 < nKeys && threadIdx.x == 0) keyStart[nKeys] = offset;
 }
 
-// Writes the provisional member list: members[keyStart[h] + provRank[i]] = i
+// Writes the provisional member list: members[keyStart[h] + provRank[i]] = i, with kRankHead set in the word of a cell's first slot
+// (provisional rank 0).  The placement finds the cells' boundaries from that bit and writes sortHash itself, in its coalesced-by-cell
+// store beside index and sortPos: written here, slot by slot, it was 4 bytes per particle of scattered stores to be read back once.
+constexpr uint kRankHead = 0x80000000u;  // (particle indices are below 2^31 - 1)
 __global__ void __launch_bounds__(kBlock) k_members(const uint *__restrict__ hash, const uint *__restrict__ provRank,
-                                                    const uint *__restrict__ keyStart, int N,
-                                                    int *__restrict__ members, uint *__restrict__ sortHash) {
+                                                    const uint *__restrict__ keyStart, int N, uint *__restrict__ members) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= N) return;
-  const uint h = hash[i];
-  const uint dst = keyStart[h] + provRank[i];
-  members[dst] = i;
-  if (sortHash) sortHash[dst] = h;  // already FINAL: all members of a cell's slot range share the key, whatever their order
+  const uint r = provRank[i];
+  members[keyStart[hash[i]] + r] = (uint)i | (r == 0u ? kRankHead : 0u);
 }
 
 // ---- counting build, second half -----------------------------------------------------------------------------------
-// Stable placement, one thread per PROVISIONAL slot: the slot's cell is known from sortHash (coalesced), its members are the
-// neighbouring slots (cache hits), the only gather left is pos[i].  Final slot = first slot of the cell + #{members with a smaller
-// index}: the order utils/ParticleSorter.cuh:156-164,303-321 (stable radix sort of the hashes) produces.  Blocks past the
+// Stable placement, one thread per PROVISIONAL slot: the slot's cell is the run of slots around it between two head bits (the
+// workgroup's LDS window, loaded coalesced), the only gather left is pos[i].  Final slot = first slot of the cell + #{members with a
+// smaller index}: the order utils/ParticleSorter.cuh:156-164,303-321 (stable radix sort of the hashes) produces.  Blocks past the
 // particle range write the per-cell tables (k_cell_tables' job) so that the build ends with this launch.
 // (Round 3 tried to do without k_members: the hash kernel wrote the members into fixed-capacity rows, one per key, and half a wave per
 // cell ranked its row through lane shuffles and scattered — lists identical, the C3 step the same to 0.2 % (0.19358 against 0.19391 ms:
 // the hash kernel's scattered row stores cost what k_members saved), a plain build 5 us slower; a particle-major form of it lost 6 us
 // to 16-byte scattered stores, and an atomicMax of every workgroup on one word cost 19 us.  Removed.)
-__global__ void __launch_bounds__(kBlock) k_rank_scatter2(const float4 *__restrict__ pos, const uint *__restrict__ sortHash,
-                                                          const uint *__restrict__ keyStart, const int *__restrict__ members,
+constexpr int kRankHalo = 32;  // slots beside the workgroup's own that its LDS window also holds: a liquid's cells (12.6 members at C3) end inside it
+constexpr int kRankPad = 4;    // kRankEdge entries at either end of the window: a walk reads four entries at a time
+constexpr int kRankWin = kBlock + 2 * kRankHalo;
+constexpr uint kRankEdge = 0xffffffffu;  // no member word: a window pad, or a slot outside [0, N); it reads as a head, so a cell ends in front of it
+static_assert(2 * kRankHalo <= 64 && 2 * kRankPad <= kBlock, "one wave loads both halos");
+// Walks a cell's slots away from the thread's own, from slot `at` on, four slots per round trip, and adds the members with an index below
+// i to rank.  Leftwards the cell ends WITH its head, rightwards IN FRONT of the next head.  Returns how many slots belonged to the cell; a
+// walk stopped by kRankEdge has run out of what fetch() can see.
+template <bool LEFT, class Fetch> UH_D int rank_walk(Fetch fetch, const int at, const int i, uint &rank) {
+  int n = 0;
+  for (;;) {
+    uint a[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = fetch(LEFT ? at - (n + u) : at + (n + u));
+    bool go = true;
+    int got = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool in = go && (LEFT ? a[u] != kRankEdge : !(a[u] & kRankHead));
+      rank += (uint)(in && (int)(a[u] & ~kRankHead) < i);
+      got += (int)in;
+      go = in && !(LEFT && (a[u] & kRankHead));
+    }
+    n += got;
+    if (!go) return n;
+  }
+}
+__global__ void __launch_bounds__(kBlock) k_rank_scatter2(const float4 *__restrict__ pos, uint *__restrict__ sortHash, GridT<float> grid,
+                                                          const uint *__restrict__ keyStart, const uint *__restrict__ members,
                                                           int N, int particleBlocks, int *__restrict__ index,
                                                           float4 *__restrict__ sortPos,
                                                           unsigned char *__restrict__ keyOutside, uint *__restrict__ keyCount,
@@ -355,21 +385,56 @@ __global__ void __launch_bounds__(kBlock) k_rank_scatter2(const float4 *__restri
     if (c == ncells - 1) cellRange[ncells] = make_uint2(0u, 0u);
     return;
   }
-  const int m = blockIdx.x * kBlock + threadIdx.x;
-  if (m >= N) return;
-  const uint h = sortHash[m];
-  const int i = members[m];
-  const float4 p = pos[i];
-  const uint s = keyStart[h], e = keyStart[h + 1];
-  uint rank = 0;
-  uint q = s;
-  for (; q + 4 <= e; q += 4) {
-    const int a = members[q], b = members[q + 1], c = members[q + 2], d = members[q + 3];
-    rank += (a < i) + (b < i) + (c < i) + (d < i);
+  // Particle blocks.  A cell's members are the slots around the thread's own, from the cell's head to the slot in front of the next head,
+  // so the workgroup loads the member words of its kBlock slots and of kRankHalo more on either side ONCE, coalesced, into LDS and
+  // every thread ranks itself there: two dependent trips to memory (slot -> position) instead of slot -> keyStart -> three or four
+  // batches of the cell's members -> store.  Neither keyStart nor a key is read here: the walk that counts the smaller indices also
+  // finds the cell's first slot, and the key that goes with the sorted position is recomputed from it.
+  __shared__ uint win[kRankWin + 2 * kRankPad];  // entry e: the member word of slot lo + e - kRankPad
+  const int tid = threadIdx.x;
+  const int base = blockIdx.x * kBlock, lo = base - kRankHalo;
+  const int m = base + tid;
+  const bool active = m < N;
+  // (the loads are unconditional, on clamped slots: behind a branch the compiler waits for ALL of them, the gather included, before the
+  // first LDS store)
+  uint w = members[min(m, N - 1)];
+  uint side = kRankEdge;
+  if (tid < 2 * kRankHalo) {  // the first wave also fetches the halo: lanes [0, kRankHalo) the left one, the rest the right one
+    const int g = tid < kRankHalo ? lo + tid : base + kBlock + (tid - kRankHalo);
+    const int gc = min(max(g, 0), N - 1);
+    side = members[gc];
+    if (g != gc) side = kRankEdge;
   }
-  for (; q < e; ++q) rank += (members[q] < i) ? 1u : 0u;
-  const uint dst = s + rank;
+  const int i = (int)(w & ~kRankHead);
+  const float4 p = pos[i];  // needs the own slot only: in flight across the barrier and the ranking
+  if (!active) w = kRankEdge;
+  const int own = kRankPad + kRankHalo + tid;
+  win[own] = w;
+  if (tid < 2 * kRankHalo) win[kRankPad + (tid < kRankHalo ? tid : kBlock + tid)] = side;
+  if (tid < 2 * kRankPad) win[tid < kRankPad ? tid : kRankWin + tid] = kRankEdge;
+  __syncthreads();
+  if (!active) return;
+  uint rank = 0;
+  const auto inWindow = [&](int e) { return win[e]; };  // (a walk goes on only from an entry that is not a pad: it reads at most four entries further)
+  int first = m;
+  if (!(w & kRankHead)) {
+    const int n = rank_walk<true>(inWindow, own - 1, i, rank);
+    first -= n;
+    // the window ended before the head did (the cell holds more than kRankHalo particles on this side of the workgroup's slots, or more
+    // than the window): the same walk over the array itself
+    if (own - n == kRankPad && !(win[kRankPad] & kRankHead))
+      first -= rank_walk<true>([&](int g) { return g >= 0 ? members[g] : kRankEdge; }, lo - 1, i, rank);
+  }
+  if (own + 1 + rank_walk<false>(inWindow, own + 1, i, rank) == kRankPad + kRankWin)
+    rank_walk<false>([&](int g) { return g < N ? members[g] : kRankEdge; }, lo + kRankWin, i, rank);
+  // the key, as the hash kernel computed it from these very bits (its clamp of a particle without a cell is the identity on every other)
+  int3 cc = grid.getCell(real3f{p.x, p.y, p.z});
+  cc.x = min(max(cc.x, 0), grid.cellDim.x - 1);
+  cc.y = min(max(cc.y, 0), grid.cellDim.y - 1);
+  cc.z = min(max(cc.z, 0), grid.cellDim.z - 1);
+  const uint dst = (uint)first + rank;
   index[dst] = i;
+  sortHash[dst] = morton_hash(cc);
   sortPos[dst] = p;
 }
 
@@ -777,10 +842,10 @@ int CellList::update(const float4 *d_pos, int numberParticles, const float L[3],
                          (unsigned long long *)scanFlags.ptr, scanGeneration, (uint *)keyStart.ptr, devErr);
     }
     hipLaunchKernelGGL(k_members, dim3(nblocks(N)), dim3(kBlock), 0, st, (const uint *)hash.ptr, (const uint *)provRank.ptr,
-                       (const uint *)keyStart.ptr, N, (int *)members.ptr, (uint *)sortHash.ptr);
+                       (const uint *)keyStart.ptr, N, (uint *)members.ptr);
     const int pb = nblocks(N);
-    hipLaunchKernelGGL(k_rank_scatter2, dim3(pb + nblocks(ncells)), dim3(kBlock), 0, st, d_pos, (const uint *)sortHash.ptr,
-                       (const uint *)keyStart.ptr, (const int *)members.ptr, N, pb, (int *)index.ptr, (float4 *)sortPos.ptr,
+    hipLaunchKernelGGL(k_rank_scatter2, dim3(pb + nblocks(ncells)), dim3(kBlock), 0, st, d_pos, (uint *)sortHash.ptr, grid,
+                       (const uint *)keyStart.ptr, (const uint *)members.ptr, N, pb, (int *)index.ptr, (float4 *)sortPos.ptr,
                        (unsigned char *)keyOutside.ptr, (uint *)keyCount.ptr, grid.cellDim, validCell, (uint *)cellStart.ptr,
                        (int *)cellEnd.ptr, (unsigned char *)cellOutside.ptr, (uint2 *)cellRange.ptr);
     zeroBlockClean = true;
