@@ -528,6 +528,28 @@ int uammd_fcm_displacements_staged(uammd_fcm *h, const float *d_pos, const float
                                    float temperature, float prefactor, float *d_linearVelocity, int stage,
                                    void *stream);
 int uammd_fcm_export_fourier(uammd_fcm *h, float *d_out6, void *stream);
+/* test hook: the solver's own batched 3-D real FFT (the LDS pipeline that serves axis lengths 2^a 3^b 5^c 7^d 11^e, x even in [16, 512],
+ * y in [2, 256], z in [2, 512]) and nothing else, in place on d_grid in the solver's layout: three planar components, each nz * ny rows
+ * of 2 * (nx / 2 + 1) floats = nx / 2 + 1 complex.  Needs no handle and builds no rocFFT plans; returns an error (and touches nothing)
+ * for any other grid.  Both directions are unnormalised.
+ *   UAMMD_FCM_FFT_FORWARD_XY   the x and y passes: the R2C over (y, x) of every plane
+ *   UAMMD_FCM_FFT_FORWARD_XYZ  ... then the forward z pass of the fused z kernel, without its operator and its inverse: the 3-D R2C
+ *   UAMMD_FCM_FFT_INVERSE_ZYX  the inverse z pass of the fused z kernel alone, the inverse y pass and the C2R rows: the 3-D C2R, into
+ *                              `target`: the planar real grids in place, or d_inter as the gather's float4 grid [nz][ny][nx] = (x, y, z, 0)
+ *                              or its packed form of three floats per node
+ * info (may be null): [0] = UAMMD_FCM_FFT_PATH_* of the forward x / y passes (-1 for the inverse), [1] = nodes per workgroup of the z pass
+ * (0 when it did not run) */
+#define UAMMD_FCM_FFT_FORWARD_XY 0
+#define UAMMD_FCM_FFT_FORWARD_XYZ 1
+#define UAMMD_FCM_FFT_INVERSE_ZYX 2
+#define UAMMD_FCM_FFT_TARGET_PLANAR 0
+#define UAMMD_FCM_FFT_TARGET_FLOAT4 1
+#define UAMMD_FCM_FFT_TARGET_PACKED 2
+#define UAMMD_FCM_FFT_PATH_ROWS_LINES 0  /* row kernel + y lines */
+#define UAMMD_FCM_FFT_PATH_PLANE_P2 1    /* a whole plane per workgroup, power-of-two instantiation */
+#define UAMMD_FCM_FFT_PATH_PLANE_DENSE 2 /* ... mixed radix, two planes per compute unit */
+#define UAMMD_FCM_FFT_PATH_PLANE_LARGE 3 /* ... mixed radix, one plane per compute unit */
+int uammd_fcm_fft_probe(const int cells[3], int mode, int target, float *d_grid, float *d_inter, int *info, void *stream);
 /* "atomic_spread" = 1 forces the one-wave-per-particle atomic spread/gather instead of the tile-owned kernels;
  * "tile_gather" = 1 selects the LDS-staged gather (supports <= 6; slower than the default at 24 particles per tile) */
 int uammd_fcm_set_option(uammd_fcm *h, const char *name, int value);

@@ -286,6 +286,27 @@ class FCM_impl:
         check(self.lib.uammd_fcm_set_seed2(self.h, int(value)))
 
 
+FFT_FORWARD_XY, FFT_FORWARD_XYZ, FFT_INVERSE_ZYX = 0, 1, 2
+FFT_TARGET_PLANAR, FFT_TARGET_FLOAT4, FFT_TARGET_PACKED = 0, 1, 2
+FFT_PATHS = {-1: "none", 0: "rows + lines", 1: "plane p2", 2: "plane two-per-CU", 3: "plane large"}
+
+
+def fft_probe(cells, mode, grid, target=FFT_TARGET_PLANAR):
+    """uammd_fcm_fft_probe: the solver's own FFT passes in place on `grid`, a contiguous float32 device tensor of shape
+    (3, nz, ny, 2 * (nx // 2 + 1)).  Returns (x/y path, z tile, inter): inter is the float4 (nz, ny, nx, 4) or packed (nz, ny, nx, 3)
+    grid of FFT_INVERSE_ZYX with that target, else None."""
+    nx, ny, nz = (int(c) for c in cells)
+    if grid.dtype != torch.float32 or not grid.is_contiguous() or tuple(grid.shape) != (3, nz, ny, 2 * (nx // 2 + 1)):
+        raise ValueError(f"fft_probe: grid must be contiguous float32 of shape {(3, nz, ny, 2 * (nx // 2 + 1))}")
+    inter = None
+    if mode == FFT_INVERSE_ZYX and target != FFT_TARGET_PLANAR:
+        inter = torch.empty((nz, ny, nx, 4 if target == FFT_TARGET_FLOAT4 else 3), dtype=torch.float32, device=grid.device)
+    info = (C.c_int * 2)(-1, 0)
+    check(_lib.load().uammd_fcm_fft_probe(i3([nx, ny, nz]), int(mode), int(target), _ptr(grid), _ptr(inter) if inter is not None else None,
+                                          info, current_stream()))
+    return int(info[0]), int(info[1]), inter
+
+
 def _initialize(par, rng):
     """detail::initializeGrid / initializeKernel (BDHI_FCM.cuh:29-66) + the ctor body of BDHI::FCM (:98-110)."""
     if par.seed == 0:

@@ -22,6 +22,7 @@
 #include "saru.hpp"
 
 #include <cmath>
+#include <memory>
 #include <string>
 
 namespace uammd_hip {
@@ -1547,7 +1548,11 @@ __global__ void __launch_bounds__(256) k_fcm_kspace(float2 *__restrict__ g0, KLa
 // all nz planes in LDS: forward z transform (skipped when there are no forces: the grid is then all noise), the Stokes / noise
 // operator node by node, inverse z transform, store.  Replaces two strided rocFFT passes and k_fcm_kspace (three trips of the
 // 25.6 MB grid through memory at C4) by one.
-template <int LOG2TL, int NT, bool P2>
+// MODE (compile time: a run-time choice in these kernels costs several per cent) cuts the kernel down for uammd_fcm_fft_probe:
+// kZForwardOnly = loads (with the fused first pass where the full kernel has it), forward transform, plain store;
+// kZInverseOnly = plain load, inverse transform (with the fused last pass into the stores where the full kernel has it).
+enum { kZFull = 0, kZForwardOnly = 1, kZInverseOnly = 2 };
+template <int LOG2TL, int NT, bool P2, int MODE = kZFull>
 __global__ void __launch_bounds__(NT) k_fft_z_fused(float2 *__restrict__ g, size_t planeC, size_t zStride, int nyl, int y0, int nzArg,
                                                     int3 nk, real3f L, float viscosity, bool haveForce, float noisePrefactor,
                                                     uint seed1, uint seed2, PseGreens pse) {
@@ -1571,7 +1576,7 @@ __global__ void __launch_bounds__(NT) k_fft_z_fused(float2 *__restrict__ g, size
   const int log2N = 31 - __builtin_clz((unsigned)nz);
   const bool edges = P2 && haveForce && nl == TL && log2N % 3 != 0 && log2N >= 5 && NLINES * (nz >> 2) <= QF * NT &&
                      NLINES * (nz >> 3) <= QL * NT;
-  if (edges) {
+  if (MODE != kZInverseOnly && edges) {
     const int per = nz >> 2, total = NLINES * per;
     float2 v[QF][4];
 #pragma unroll
@@ -1611,9 +1616,10 @@ __global__ void __launch_bounds__(NT) k_fft_z_fused(float2 *__restrict__ g, size
           });
     }
     __syncthreads();
-    fft_lds<-1, MAXB, NT, P2>(buf, LS, nz, 3 * nl, tw, 1, tid);
+    if constexpr (MODE != kZInverseOnly) fft_lds<-1, MAXB, NT, P2>(buf, LS, nz, 3 * nl, tw, 1, tid);
   } else
     __syncthreads();
+  if constexpr (MODE == kZFull) {
   if (l < nl) {
     const int q = q0 + l, yl = q / nkx, kx = q - yl * nkx, ky = y0 + yl;
     for (int j = jg; j < nz; j += JG) {
@@ -1629,7 +1635,8 @@ __global__ void __launch_bounds__(NT) k_fft_z_fused(float2 *__restrict__ g, size
     }
   }
   __syncthreads();
-  if (edges) {
+  }
+  if (MODE != kZForwardOnly && edges) {
     fft_lds_p2_inner<1, MAXB, NT>(buf, LS, log2N, NLINES, tw, 1, tid, false, true);
     const int per = nz >> 3, total = NLINES * per;   // the last pass: radix 8, sub-transforms of nz / 8 points, outputs at j + r nz / 8
 #pragma unroll
@@ -1651,7 +1658,7 @@ __global__ void __launch_bounds__(NT) k_fft_z_fused(float2 *__restrict__ g, size
     }
     return;
   }
-  fft_lds<1, MAXB, NT, P2>(buf, LS, nz, 3 * nl, tw, 1, tid);
+  if constexpr (MODE != kZForwardOnly) fft_lds<1, MAXB, NT, P2>(buf, LS, nz, 3 * nl, tw, 1, tid);
   if (l < nl)
     for (int c = 0; c < 3; ++c)
       for (int j = jg; j < nz; j += JG) base[(size_t)c * planeC + (size_t)j * slab] = buf[(c * nl + l) * LS + j];
@@ -1738,8 +1745,10 @@ static bool fcm_plane_fft_usable(int nx, int ny) {
          fcm_plane_fft_lds(nx, ny) <= (size_t)std::min(ldsLimit, 96 * 1024);
 }
 // forward x and y transforms of the three real component grids, in place
-static int fcm_fft_forward_xy(FCM *f, float *g, hipStream_t st) {
+// (path, for uammd_fcm_fft_probe: which kernels ran — UAMMD_FCM_FFT_PATH_*)
+static int fcm_fft_forward_xy(FCM *f, float *g, hipStream_t st, int *path = nullptr) {
   const int nx = f->grid.cellDim.x, ny = f->grid.cellDim.y, nz = f->grid.cellDim.z, nkx = nx / 2 + 1, nh = nx / 2;
+  if (path) *path = UAMMD_FCM_FFT_PATH_ROWS_LINES;
   if (fcm_plane_fft_usable(nx, ny)) {  // one pass: a whole plane per workgroup
     const size_t lds = fcm_plane_fft_lds(nx, ny);
     static bool attrSet[64] = {false};  // (a function attribute belongs to the device's copy of the kernel)
@@ -1751,6 +1760,7 @@ static int fcm_fft_forward_xy(FCM *f, float *g, hipStream_t st) {
       UH_CHECK(hipFuncSetAttribute((const void *)k_fft_xy_r2c_plane<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
       if (dev >= 0 && dev < 64) attrSet[dev] = true;
     }
+    if (path) *path = is_pow2(nx) && is_pow2(ny) ? UAMMD_FCM_FFT_PATH_PLANE_P2 : (lds <= 80 * 1024 ? UAMMD_FCM_FFT_PATH_PLANE_DENSE : UAMMD_FCM_FFT_PATH_PLANE_LARGE);
     if (is_pow2(nx) && is_pow2(ny)) hipLaunchKernelGGL(k_fft_xy_r2c_plane<true>, dim3(3 * nz), dim3(kPlaneThreads), lds, st, g, nx, ny);
     else if (lds <= 80 * 1024) hipLaunchKernelGGL((k_fft_xy_r2c_plane<false, true>), dim3(3 * nz), dim3(kPlaneThreads), lds, st, g, nx, ny);   // two planes per CU
     else hipLaunchKernelGGL(k_fft_xy_r2c_plane<false>, dim3(3 * nz), dim3(kPlaneThreads), lds, st, g, nx, ny);
@@ -1772,30 +1782,45 @@ static int fcm_fft_forward_xy(FCM *f, float *g, hipStream_t st) {
 #ifndef UAMMD_ZG_THREADS
 #define UAMMD_ZG_THREADS 256
 #endif
+// (mode != kZFull, for uammd_fcm_fft_probe: the forward or the inverse transform alone, at the default tile; tile: the nodes per workgroup)
 static int fcm_fft_z_fused_launch(FCM *f, float2 *g, size_t planeC, size_t zStride, int nyl, int y0, int3 cells, real3f L, bool haveForce,
-                                  float noisePrefactor, uint seed2, hipStream_t st) {
+                                  float noisePrefactor, uint seed2, hipStream_t st, int mode = kZFull, int *tile = nullptr) {
   const int nz = cells.z, nkx = cells.x / 2 + 1, lines = nyl * nkx;
   // tile of (ky, kx) nodes per workgroup: 3 tl nz complex in LDS and <= 6 radix-4 butterflies per thread and pass
   int ltl = nz <= 256 ? 3 : 2;  // measured at C4: 8 nodes x 512 threads
-  if (f->zTileLog2 > 0 && sizeof(float2) * (size_t)(nz + 3 * (1 << f->zTileLog2) * (nz + 1)) <= 64 * 1024) ltl = f->zTileLog2;  // (tuning option)
+  if (mode == kZFull && f->zTileLog2 > 0 && sizeof(float2) * (size_t)(nz + 3 * (1 << f->zTileLog2) * (nz + 1)) <= 64 * 1024) ltl = f->zTileLog2;  // (tuning option)
   const int tlz = 1 << ltl;
   const size_t ldsz = sizeof(float2) * (size_t)(nz + 3 * tlz * (nz + 1));
   const dim3 gz((lines + tlz - 1) / tlz), bz(512);
+  if (tile) *tile = tlz;
 #ifndef UAMMD_ZP_THREADS
 #define UAMMD_ZP_THREADS 512
 #endif
-#define UH_ZFUSED(LT, P) hipLaunchKernelGGL((k_fft_z_fused<LT, UAMMD_ZP_THREADS, P>), gz, dim3(UAMMD_ZP_THREADS), ldsz, st, g, planeC, zStride, nyl, y0, nz, cells, L, f->par.viscosity, \
+#define UH_ZFUSED_M(LT, P, M) hipLaunchKernelGGL((k_fft_z_fused<LT, UAMMD_ZP_THREADS, P, M>), gz, dim3(UAMMD_ZP_THREADS), ldsz, st, g, planeC, zStride, nyl, y0, nz, cells, L, f->par.viscosity, \
                                          haveForce, noisePrefactor, f->par.seed, seed2, f->pse)
-  if (is_pow2(nz)) { if (ltl == 4) UH_ZFUSED(4, true); else if (ltl == 3) UH_ZFUSED(3, true); else UH_ZFUSED(2, true); }
+#define UH_ZFUSED(LT, P) UH_ZFUSED_M(LT, P, kZFull)
+#define UH_ZFUSED_GM(LT, M) hipLaunchKernelGGL((k_fft_z_fused<LT, UAMMD_ZG_THREADS, false, M>), gz, dim3(UAMMD_ZG_THREADS), ldsz, st, g, planeC, zStride, nyl, y0, nz, \
+                                           cells, L, f->par.viscosity, haveForce, noisePrefactor, f->par.seed, seed2, f->pse)
+  if (mode != kZFull) {  // the probe's instantiations: the default tiles only (8 nodes up to 256 planes, 4 above)
+    const bool fwd = mode == kZForwardOnly;
+    if (is_pow2(nz)) {
+      if (ltl == 3) { if (fwd) UH_ZFUSED_M(3, true, kZForwardOnly); else UH_ZFUSED_M(3, true, kZInverseOnly); }
+      else { if (fwd) UH_ZFUSED_M(2, true, kZForwardOnly); else UH_ZFUSED_M(2, true, kZInverseOnly); }
+    } else {
+      if (ltl == 3) { if (fwd) UH_ZFUSED_GM(3, kZForwardOnly); else UH_ZFUSED_GM(3, kZInverseOnly); }
+      else { if (fwd) UH_ZFUSED_GM(2, kZForwardOnly); else UH_ZFUSED_GM(2, kZInverseOnly); }
+    }
+  } else if (is_pow2(nz)) { if (ltl == 4) UH_ZFUSED(4, true); else if (ltl == 3) UH_ZFUSED(3, true); else UH_ZFUSED(2, true); }
   else {
     // (mixed-radix lines: a radix-12 or radix-9 pass has 3 tl nz / 12 .. / 9 butterflies — 216 and 288 at 108 — for 512 threads; with 256
     // threads per workgroup the passes fill their waves and the LDS, not the thread count, sets how many tiles a CU holds)
-#define UH_ZFUSED_G(LT) hipLaunchKernelGGL((k_fft_z_fused<LT, UAMMD_ZG_THREADS, false>), gz, dim3(UAMMD_ZG_THREADS), ldsz, st, g, planeC, zStride, nyl, y0, nz, \
-                                           cells, L, f->par.viscosity, haveForce, noisePrefactor, f->par.seed, seed2, f->pse)
+#define UH_ZFUSED_G(LT) UH_ZFUSED_GM(LT, kZFull)
     if (ltl == 4) UH_ZFUSED_G(4); else if (ltl == 3) UH_ZFUSED_G(3); else UH_ZFUSED_G(2);
 #undef UH_ZFUSED_G
   }
 #undef UH_ZFUSED
+#undef UH_ZFUSED_M
+#undef UH_ZFUSED_GM
   return 0;
 }
 static int fcm_fft_z_operator_y(FCM *f, float *g, bool haveForce, float noisePrefactor, hipStream_t st) {
@@ -2027,6 +2052,54 @@ int uammd_fcm_export_fourier(uammd_fcm *h, float *d_out6, void *stream) {
   hipLaunchKernelGGL(k_fcm_export, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const float2 *)f->gridBuf.ptr, f->planeCplx, total, d_out6);
   UH_CHECK(hipGetLastError());
+  return 0;
+}
+
+// The pipeline's transforms and nothing else, in place on the caller's grids (include/uammd_hip.h): no handle and no rocFFT plans — a
+// default FCM that carries the grid and its padded layout through the launchers the solver uses.
+int uammd_fcm_fft_probe(const int cells[3], int mode, int target, float *d_grid, float *d_inter, int *info, void *stream) {
+  if (!cells || !d_grid) { set_last_error("uammd_fcm_fft_probe: null argument"); return -1; }
+  if (mode != UAMMD_FCM_FFT_FORWARD_XY && mode != UAMMD_FCM_FFT_FORWARD_XYZ && mode != UAMMD_FCM_FFT_INVERSE_ZYX) {
+    set_last_error("uammd_fcm_fft_probe: mode = %d", mode);
+    return -1;
+  }
+  const bool inverse = mode == UAMMD_FCM_FFT_INVERSE_ZYX;
+  if (inverse && target != UAMMD_FCM_FFT_TARGET_PLANAR && target != UAMMD_FCM_FFT_TARGET_FLOAT4 && target != UAMMD_FCM_FFT_TARGET_PACKED) {
+    set_last_error("uammd_fcm_fft_probe: target = %d", target);
+    return -1;
+  }
+  if (inverse && target != UAMMD_FCM_FFT_TARGET_PLANAR && !d_inter) { set_last_error("uammd_fcm_fft_probe: this target needs d_inter"); return -1; }
+  if (cells[0] < 1 || cells[1] < 1 || cells[2] < 1) { set_last_error("uammd_fcm_fft_probe: cells = %d x %d x %d", cells[0], cells[1], cells[2]); return -2; }
+  std::unique_ptr<FCM> f(new FCM());
+  f->par = uammd_fcm_parameters{};
+  f->par.viscosity = 1.0f;
+  for (int a = 0; a < 3; ++a) { f->par.cells[a] = cells[a]; f->par.boxSize[a] = (float)cells[a]; }
+  const int periodic[3] = {1, 1, 1};
+  f->grid = make_grid<float>(make_box<float>(f->par.boxSize, periodic), make_int3(cells[0], cells[1], cells[2]));
+  fft_padded_layout(3, cells, &f->nxpad, &f->planeReal, &f->planeCplx);
+  if (!fcm_custom_fft_usable(f.get())) {
+    set_last_error("uammd_fcm_fft_probe: %d x %d x %d is not a grid the LDS transforms serve (2^a 3^b 5^c 7^d 11^e with x even in [16, 512], "
+                   "y in [2, 256], z in [2, 512])", cells[0], cells[1], cells[2]);
+    return -2;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const int ny = cells[1], nz = cells[2], nkx = cells[0] / 2 + 1;
+  const real3f L{f->par.boxSize[0], f->par.boxSize[1], f->par.boxSize[2]};
+  int path = -1, tile = 0;
+  if (!inverse) {
+    if (int e = fcm_fft_forward_xy(f.get(), d_grid, st, &path)) return e;
+    if (mode == UAMMD_FCM_FFT_FORWARD_XYZ)
+      if (int e = fcm_fft_z_fused_launch(f.get(), (float2 *)d_grid, f->planeCplx, (size_t)ny * nkx, ny, 0, f->grid.cellDim, L, true, 0.0f, 0u, st,
+                                         kZForwardOnly, &tile)) return e;
+  } else {
+    if (int e = fcm_fft_z_fused_launch(f.get(), (float2 *)d_grid, f->planeCplx, (size_t)ny * nkx, ny, 0, f->grid.cellDim, L, true, 0.0f, 0u, st,
+                                       kZInverseOnly, &tile)) return e;
+    fft_launch_lines<1>((float2 *)d_grid, ny, nkx, 3 * nz, st);
+    if (int e = fcm_fft_inverse_x(f.get(), d_grid, target == UAMMD_FCM_FFT_TARGET_PLANAR ? nullptr : (float4 *)d_inter, st,
+                                  target == UAMMD_FCM_FFT_TARGET_PACKED)) return e;
+  }
+  UH_CHECK(hipGetLastError());
+  if (info) { info[0] = path; info[1] = tile; }
   return 0;
 }
 
