@@ -744,6 +744,24 @@ int uammd_poisson_sum(uammd_poisson *h, const float *d_pos, const float *d_charg
  * zero-fills it first).  d_force / d_energy (nullable) receive the far-field side effect the reference's call has. */
 int uammd_poisson_field_potential(uammd_poisson *h, const float *d_pos, const float *d_charge, int numberParticles,
                                   float *d_fieldPotential, float *d_force, float *d_energy, void *stream);
+/* test hook: one stage of the far field alone, through the host functions and launches uammd_poisson_sum uses (the grids are
+ * [nz][ny][2*(nx/2+1)], the layout of the in-place transforms):
+ *   UAMMD_POISSON_PROBE_SPREAD    cell list, pack, spread of the charges ("atomic_spread" is honoured); d_out: the charge grid, float
+ *   UAMMD_POISSON_PROBE_CONVOLVE  d_in: a charge grid; forward transform, Fourier-space kernel, the four inverse transforms and the
+ *                                 interleave; d_out: the float4 grid (Ex, Ey, Ez, phi).  Needs no particles.
+ *   UAMMD_POISSON_PROBE_GATHER    d_in: a float4 grid; cell list, pack, gather: (E, phi) is ADDED to d_out (real4[N]), q E to d_force
+ *                                 (real4[N], nullable) and q phi to d_energy (real[N], nullable), as uammd_poisson_field_potential does
+ * d_force and d_energy are consulted by the gather only.  info (may be null) reports what ran: [0..2] = tile dimensions of the
+ * tile-owned spread, [3] = its waves per workgroup (0: the atomic spread ran), [4] = the compile-time support of its instantiation
+ * (0: the generic body), [5] = UAMMD_POISSON_GATHER_*; entries of a stage that did not run are -1. */
+#define UAMMD_POISSON_PROBE_SPREAD 0
+#define UAMMD_POISSON_PROBE_CONVOLVE 1
+#define UAMMD_POISSON_PROBE_GATHER 2
+#define UAMMD_POISSON_GATHER_COL1 1 /* one stencil column per lane */
+#define UAMMD_POISSON_GATHER_COL2 2 /* two columns per lane */
+#define UAMMD_POISSON_GATHER_FLAT 3 /* node by node */
+int uammd_poisson_probe(uammd_poisson *h, int stage, const float *d_pos, const float *d_charge, int numberParticles, const float *d_in,
+                        float *d_out, float *d_force, float *d_energy, int *info, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Path B on several GPUs — z-slab decomposition of the FCM grid (the reference is single GPU, so these

@@ -349,6 +349,7 @@ SIGNATURES = {
     "uammd_poisson_set_option": (_i, [_vp, C.c_char_p, _i]),
     "uammd_poisson_sum": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "uammd_poisson_field_potential": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "uammd_poisson_probe": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp]),
     "uammd_fcm_create": (_i, [C.POINTER(FCMParameters), C.POINTER(_vp)]),
     "uammd_fcm_destroy": (_i, [_vp]),
     "uammd_fcm_displacements": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp]),

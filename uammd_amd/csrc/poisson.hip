@@ -687,14 +687,21 @@ static int poisson_bin(Poisson *p, Poisson::TileSet &ts, int N, hipStream_t st) 
   return 0;
 }
 
-// farField (.cu:332-360): any of d_force / d_energy / d_fieldPotential may be null
-// (the particles have been sorted and packed by poisson_list)
-static int poisson_far(Poisson *p, int N, float *d_force, float *d_energy, float *d_fieldPotential, hipStream_t st) {
+// farField (.cu:332-360) in its three parts: spread, Fourier-space solve, gather (the particles have been sorted and packed by
+// poisson_list).  uammd_poisson_probe runs them one at a time; `ran`, when given, receives what was launched.
+struct PoissonRan {
+  int tile[3] = {-1, -1, -1};
+  int waves = -1, S = -1, gather = -1;
+};
+
+// spread q into gridQ
+static int poisson_spread(Poisson *p, int N, hipStream_t st, PoissonRan *ran = nullptr) {
   float *gq = (float *)p->gridQ.ptr;
   const FastDiv dsx = make_fastdiv(p->kern.support.x), dsxy = make_fastdiv(p->kern.support.x * p->kern.support.y);
   const int s = p->kern.support.x;
   UH_CHECK(hipMemsetAsync(gq, 0, sizeof(float) * p->planeReal, st));
   const bool tileSpread = p->spreadTiles.on && !p->forceAtomicSpread;
+  if (ran) ran->tile[0] = ran->tile[1] = ran->tile[2] = ran->waves = ran->S = 0;
   if (tileSpread) {
     Poisson::TileSet &ts = p->spreadTiles;
     if (int e = poisson_bin(p, ts, N, st)) return e;
@@ -703,7 +710,9 @@ static int poisson_far(Poisson *p, int N, float *d_force, float *d_energy, float
     const float4 *tp = (const float4 *)ts.pos.ptr;
     const int *tst = (const int *)ts.start.ptr;
     const dim3 g(ts.numTiles()), b(64 * ts.waves);
-#define UH_SPREAD(S_) hipLaunchKernelGGL((k_poisson_spread_tile<S_>), g, b, lds, st, tp, tst, gq, p->grid, p->nxpad, p->kern, tg)
+    if (ran) { ran->tile[0] = ts.tile.x; ran->tile[1] = ts.tile.y; ran->tile[2] = ts.tile.z; ran->waves = ts.waves; }
+#define UH_SPREAD(S_) { hipLaunchKernelGGL((k_poisson_spread_tile<S_>), g, b, lds, st, tp, tst, gq, p->grid, p->nxpad, p->kern, tg); \
+                        if (ran) ran->S = S_; }
     switch (s) {
       case 7: UH_SPREAD(7); break;
       case 8: UH_SPREAD(8); break;
@@ -718,6 +727,13 @@ static int poisson_far(Poisson *p, int N, float *d_force, float *d_energy, float
     hipLaunchKernelGGL(k_poisson_spread, dim3((N + 3) / 4), dim3(256), 0, st, (const float4 *)p->packed.ptr, gq, N, p->grid,
                        p->nxpad, p->kern, dsx, dsxy);
   }
+  UH_CHECK(hipGetLastError());
+  return 0;
+}
+
+// gridQ -> R2C -> (E, phi)(k) -> 4 x C2R -> the float4 grid `inter`
+static int poisson_convolve(Poisson *p, hipStream_t st) {
+  float *gq = (float *)p->gridQ.ptr;
   if (int e = p->fft.set_stream((void *)st)) return e;
   if (int e = p->fft.forward(gq)) return e;
   const int3 n = p->grid.cellDim;
@@ -729,20 +745,33 @@ static int poisson_far(Poisson *p, int N, float *d_force, float *d_energy, float
   const uint nreal = (uint)p->planeReal;
   hipLaunchKernelGGL(k_poisson_interleave, dim3((nreal + 255) / 256), dim3(256), 0, st, (const float *)p->planes.ptr, p->planeReal,
                      (float4 *)p->inter.ptr, nreal);
-  {
-    const int cols = p->kern.support.x * p->kern.support.y, wts = p->kern.support.x + p->kern.support.y + p->kern.support.z;
-    const bool colForm = !getenv("UAMMD_POISSON_FLAT_GATHER") && cols <= 128 && wts <= 64 &&
-                         (size_t)p->nxpad * p->grid.cellDim.y * p->grid.cellDim.z < ((size_t)1 << 31);
-#define UH_PGATHER(K, ...) hipLaunchKernelGGL(K, dim3((N + 3) / 4), dim3(256), 0, st, (const float4 *)p->packed.ptr, (const int *)p->cl.index.ptr, \
-                                              (const float4 *)p->inter.ptr, (float4 *)d_force, d_energy, (float4 *)d_fieldPotential, N, p->grid,  \
-                                              p->nxpad, p->kern, __VA_ARGS__)
-    if (colForm && cols <= 64) UH_PGATHER(k_poisson_gather_col<1>, dsx);
-    else if (colForm) UH_PGATHER(k_poisson_gather_col<2>, dsx);
-    else UH_PGATHER(k_poisson_gather, dsx, dsxy);
-#undef UH_PGATHER
-  }
   UH_CHECK(hipGetLastError());
   return 0;
+}
+
+// gather of the float4 grid `grid4`: any of d_force / d_energy / d_fieldPotential may be null
+static int poisson_gather(Poisson *p, int N, const float4 *grid4, float *d_force, float *d_energy, float *d_fieldPotential,
+                          hipStream_t st, PoissonRan *ran = nullptr) {
+  const FastDiv dsx = make_fastdiv(p->kern.support.x), dsxy = make_fastdiv(p->kern.support.x * p->kern.support.y);
+  const int cols = p->kern.support.x * p->kern.support.y, wts = p->kern.support.x + p->kern.support.y + p->kern.support.z;
+  const bool colForm = !getenv("UAMMD_POISSON_FLAT_GATHER") && cols <= 128 && wts <= 64 &&
+                       (size_t)p->nxpad * p->grid.cellDim.y * p->grid.cellDim.z < ((size_t)1 << 31);
+#define UH_PGATHER(K, ...) hipLaunchKernelGGL(K, dim3((N + 3) / 4), dim3(256), 0, st, (const float4 *)p->packed.ptr, (const int *)p->cl.index.ptr, \
+                                              grid4, (float4 *)d_force, d_energy, (float4 *)d_fieldPotential, N, p->grid,                        \
+                                              p->nxpad, p->kern, __VA_ARGS__)
+  if (colForm && cols <= 64) UH_PGATHER(k_poisson_gather_col<1>, dsx);
+  else if (colForm) UH_PGATHER(k_poisson_gather_col<2>, dsx);
+  else UH_PGATHER(k_poisson_gather, dsx, dsxy);
+#undef UH_PGATHER
+  if (ran) ran->gather = colForm ? (cols <= 64 ? UAMMD_POISSON_GATHER_COL1 : UAMMD_POISSON_GATHER_COL2) : UAMMD_POISSON_GATHER_FLAT;
+  UH_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int poisson_far(Poisson *p, int N, float *d_force, float *d_energy, float *d_fieldPotential, hipStream_t st) {
+  if (int e = poisson_spread(p, N, st)) return e;
+  if (int e = poisson_convolve(p, st)) return e;
+  return poisson_gather(p, N, (const float4 *)p->inter.ptr, d_force, d_energy, d_fieldPotential, st);
 }
 
 // nl->update(box, nearFieldCutOff) + pack (x, y, z, q) in sorted order
@@ -888,7 +917,12 @@ int uammd_poisson_create(const uammd_poisson_parameters *par, uammd_poisson **ou
       while ((ts.plane - ts.row * support) % 32 != 0) ++ts.plane;
       const size_t copyBytes = sizeof(float) * (size_t)ts.plane * (t[2] + support - 1);
       ts.waves = (int)std::min<size_t>(4, 65536 / copyBytes);
-      ts.on = ts.waves >= 1;
+      // The flush and tile_weights wrap a halo node ONCE (origin in [0, n) plus at most support - 1), which is only a node of
+      // the grid while support <= n + 1: the tiles are used when that holds on all three axes.  The constructor bounds the
+      // support by cells[0] alone, as the reference does, so a thin box can have a window wider than a short axis; it takes
+      // the atomic spread, whose centred stencil stays inside one wrap (as the reference's per-node pbc_cell) up to ~2 n.
+      const bool oneWrap = support <= p->cells[0] + 1 && support <= p->cells[1] + 1 && support <= p->cells[2] + 1;
+      ts.on = ts.waves >= 1 && oneWrap;
       if (ts.on) {
         ts.tile = make_int3(t[0], t[1], t[2]);
         ts.ntiles = make_int3(p->cells[0] / t[0], p->cells[1] / t[1], p->cells[2] / t[2]);
@@ -929,7 +963,6 @@ int uammd_poisson_sum(uammd_poisson *h, const float *d_pos, const float *d_charg
   if (N <= 0) return 0;
   if (!d_pos || !d_charge) { set_last_error("uammd_poisson_sum: null argument"); return -1; }
   if ((nearForce && !d_force) || (nearEnergy && !d_energy)) { set_last_error("uammd_poisson_sum: missing output array"); return -1; }
-  if (N <= 0) return 0;
   Poisson *p = reinterpret_cast<Poisson *>(h);
   hipStream_t st = (hipStream_t)stream;
   if (int e = poisson_list(p, d_pos, d_charge, N, st)) return e;
@@ -948,13 +981,46 @@ int uammd_poisson_field_potential(uammd_poisson *h, const float *d_pos, const fl
   if (!h) { set_last_error("uammd_poisson_field_potential: null argument"); return -1; }
   if (N <= 0) return 0;
   if (!d_pos || !d_charge || !d_fieldPotential) { set_last_error("uammd_poisson_field_potential: null argument"); return -1; }
-  if (N <= 0) return 0;
   Poisson *p = reinterpret_cast<Poisson *>(h);
   hipStream_t st = (hipStream_t)stream;
   if (int e = poisson_list(p, d_pos, d_charge, N, st)) return e;
   if (int e = poisson_far(p, N, d_force, d_energy, d_fieldPotential, st)) return e;
   if (p->par.split > 0) {
     if (int e = poisson_near<2>(p, N, d_fieldPotential, st)) return e;
+  }
+  return 0;
+}
+
+int uammd_poisson_probe(uammd_poisson *h, int stage, const float *d_pos, const float *d_charge, int N, const float *d_in, float *d_out,
+                        float *d_force, float *d_energy, int *info, void *stream) {
+  if (!h || !d_out) { set_last_error("uammd_poisson_probe: null argument"); return -1; }
+  Poisson *p = reinterpret_cast<Poisson *>(h);
+  hipStream_t st = (hipStream_t)stream;
+  PoissonRan ran;
+  if (stage == UAMMD_POISSON_PROBE_CONVOLVE) {
+    if (!d_in) { set_last_error("uammd_poisson_probe: null argument"); return -1; }
+    UH_CHECK(hipMemcpyAsync(p->gridQ.ptr, d_in, sizeof(float) * p->planeReal, hipMemcpyDeviceToDevice, st));
+    if (int e = poisson_convolve(p, st)) return e;
+    UH_CHECK(hipMemcpyAsync(d_out, p->inter.ptr, sizeof(float4) * p->planeReal, hipMemcpyDeviceToDevice, st));
+  } else if (stage == UAMMD_POISSON_PROBE_SPREAD || stage == UAMMD_POISSON_PROBE_GATHER) {
+    if (N <= 0 || !d_pos || !d_charge || (stage == UAMMD_POISSON_PROBE_GATHER && !d_in)) {
+      set_last_error("uammd_poisson_probe: this stage needs particles%s", stage == UAMMD_POISSON_PROBE_GATHER ? " and a grid" : "");
+      return -1;
+    }
+    if (int e = poisson_list(p, d_pos, d_charge, N, st)) return e;
+    if (stage == UAMMD_POISSON_PROBE_SPREAD) {
+      if (int e = poisson_spread(p, N, st, &ran)) return e;
+      UH_CHECK(hipMemcpyAsync(d_out, p->gridQ.ptr, sizeof(float) * p->planeReal, hipMemcpyDeviceToDevice, st));
+    } else {
+      if (int e = poisson_gather(p, N, (const float4 *)d_in, d_force, d_energy, d_out, st, &ran)) return e;
+    }
+  } else {
+    set_last_error("uammd_poisson_probe: unknown stage %d", stage);
+    return -1;
+  }
+  if (info) {
+    for (int a = 0; a < 3; ++a) info[a] = ran.tile[a];
+    info[3] = ran.waves; info[4] = ran.S; info[5] = ran.gather;
   }
   return 0;
 }

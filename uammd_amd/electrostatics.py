@@ -70,6 +70,33 @@ class Poisson(Interactor):
                                                      current_stream()))
         return out
 
+    SPREAD, CONVOLVE, GATHER = 0, 1, 2
+    GATHER_FORMS = {1: "col1", 2: "col2", 3: "flat"}
+
+    def probe(self, stage, pos=None, charge=None, grid=None, fieldPotential=None, force=None, energy=None):
+        """Test hook (uammd_poisson_probe): one stage of the far field alone, on the caller's device arrays instead of pd's.
+        SPREAD (pos, charge) -> the charge grid float[nz][ny][nxpad]; CONVOLVE (grid: a charge grid) -> the float4 grid
+        [nz][ny][nxpad][4]; GATHER (pos, charge, grid: a float4 grid) adds to fieldPotential (created as zeros if None) and to the
+        optional force / energy.  Returns (result, info): info = dict(tile, waves, S, gather) of what ran (tile-owned spread: waves > 0,
+        S = 0 for the generic body; gather: 'col1', 'col2' or 'flat')."""
+        nx, ny, nz = self.cells
+        nxpad = 2 * (nx // 2 + 1)
+        n = 0 if pos is None else int(pos.shape[0])
+        if stage == self.SPREAD:
+            out = torch.empty((nz, ny, nxpad), dtype=torch.float32, device="cuda")
+        elif stage == self.CONVOLVE:
+            out = torch.empty((nz, ny, nxpad, 4), dtype=torch.float32, device="cuda")
+        else:
+            out = torch.zeros((n, 4), dtype=torch.float32, device="cuda") if fieldPotential is None else fieldPotential
+        if grid is not None:
+            want = (nz, ny, nxpad) if stage == self.CONVOLVE else (nz, ny, nxpad, 4)
+            if tuple(grid.shape) != want or grid.dtype != torch.float32 or not grid.is_contiguous():
+                raise ValueError(f"probe: grid must be a contiguous float32 array of shape {want}")
+        info = (C.c_int * 6)()
+        check(self.lib.uammd_poisson_probe(self.h, int(stage), _ptr(pos), _ptr(charge), n, _ptr(grid), _ptr(out), _ptr(force),
+                                           _ptr(energy), info, current_stream()))
+        return out, dict(tile=(info[0], info[1], info[2]), waves=info[3], S=info[4], gather=self.GATHER_FORMS.get(info[5]))
+
 
 class DPPoissonSlab(Interactor):
     """DPPoissonSlab(pd, par) — Interactor/DoublyPeriodic/DPPoissonSlab.cuh:17-96: charges between two walls at z = +-H/2, periodic in x
