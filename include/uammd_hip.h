@@ -850,6 +850,11 @@ int uammd_pse_near_pair_records(uammd_pse_near *h, long long *records, long long
  * that streamed the records).  Same pairs as a build per step, summed in another order.  0 = a list build per step.
  * uammd_pse_near_list_stats: {builds from scratch, record builds from a kept list, repeated builds, 1 while the mechanism is on}. */
 int uammd_pse_near_list_stats(uammd_pse_near *h, long long out[4]);
+/* diagnostics: the product kernel the handle launched last — 0 none yet, 1 the thread-per-particle walk ("exact_order"), 2 eight lanes per
+ * particle scanning the cells, 3 pair records, 4 a wave per cell ("near_kernel" 0), 5 pair records fused with the Lanczos recurrence,
+ * 6 the same with the uammd_pse_near_set_mdot_rider product riding along (a solve whose first product carried the rider reports 6 until
+ * the handle's next product outside it).  Host-side bookkeeping: tests assert from it which path a set of options really took. */
+int uammd_pse_near_last_product(uammd_pse_near *h, int *kind);
 /* One-shot: the NEXT uammd_pse_near_stochastic on the handle also performs uammd_pse_near_mdot(h, pos, d_force, N, d_MF) with its own
  * positions — BDHI_PSE.cuh:92-126 calls the two back to back on the same list.  Where the solve streams pair records its first product
  * applies them to F as a second right-hand side (the records are read once for both vectors); otherwise (T = 0, scanning products) the

@@ -96,6 +96,9 @@ struct PSENear {
   float *riderMF = nullptr;
   bool riderArmed = false, riderLaunched = false;
   DeviceBuffer riderFs, riderMFs;   // F and M_near F in the list's order (real3)
+  // uammd_pse_near_last_product: which product kernel the handle launched last (host-side bookkeeping only) — 0 none, 1 k_pse_near,
+  // 2 k_pse_near8, 3 k_pse_near_pairs, 4 k_pse_near_cell, 5 k_pse_near_pairs_lanczos<false>, 6 k_pse_near_pairs_lanczos<true>
+  int lastProduct = 0;
   ~PSENear() {
     if (lanczos) uammd_lanczos_destroy(lanczos);
     if (pairTotalHost) (void)hipHostFree(pairTotalHost);
@@ -1280,6 +1283,7 @@ static int g_ablate = getenv("UAMMD_PSE_ABLATE") ? atoi(getenv("UAMMD_PSE_ABLATE
         const dim3 gp((N + kNearBlock / kNearGroup - 1) / (kNearBlock / kNearGroup));                                                \
         hipLaunchKernelGGL((k_pse_near_pairs<VS, IND, ACC>), gp, dim3(kNearBlock), 0, st, (const float4 *)p->recA.ptr,               \
                            (const float2 *)p->recB.ptr, (const int2 *)p->pairRange.ptr, d_v, (const int *)p->cl.index.ptr, N, d_Mv); \
+        p->lastProduct = 3;                                                                                                          \
         break;                                                                                                                       \
       }                                                                                                                              \
     }                                                                                                                                \
@@ -1296,6 +1300,7 @@ static int g_ablate = getenv("UAMMD_PSE_ABLATE") ? atoi(getenv("UAMMD_PSE_ABLATE
                            (const int *)p->cl.index.ptr, (const uint *)p->cl.cellStart.ptr, (const int *)p->cl.cellEnd.ptr,          \
                            p->cl.validCell, ncells, p->cl.grid, Lb, p->shear, p->rcut * p->rcut, make_view(p),                       \
                            (const float4 *)p->table4.ptr, d_Mv, g_ablate);                                                                     \
+      p->lastProduct = 4;                                                                                                            \
       break;                                                                                                                         \
     }                                                                                                                                \
     const dim3 gr((N + kNearBlock / kNearGroup - 1) / (kNearBlock / kNearGroup));                                                    \
@@ -1307,6 +1312,7 @@ static int g_ablate = getenv("UAMMD_PSE_ABLATE") ? atoi(getenv("UAMMD_PSE_ABLATE
       hipLaunchKernelGGL((k_pse_near8<VS, IND, ACC, false>), gr, dim3(kNearBlock), 0, st, (const float4 *)p->cl.sortPos.ptr, d_v,    \
                          (const int *)p->cl.index.ptr, (const uint *)p->cl.cellStart.ptr, (const int *)p->cl.cellEnd.ptr,            \
                          p->cl.validCell, N, p->cl.grid, Lb, p->shear, p->rcut * p->rcut, make_view(p), d_Mv);                       \
+    p->lastProduct = 2;                                                                                                              \
   } while (0)
 
 // d_Mv (+)= M_near v with v and Mv in the caller's particle order (stride VSTRIDE / 3)
@@ -1326,6 +1332,7 @@ static int pse_dot(PSENear *p, const float *d_v, float *d_Mv, hipStream_t st) {
   hipLaunchKernelGGL(k_pse_near, dim3((N + 127) / 128), dim3(128), 0, st, (const float4 *)p->cl.sortPos.ptr,
                      (const float4 *)p->sortV.ptr, (const int *)p->cl.index.ptr, (const uint *)p->cl.cellStart.ptr,
                      (const int *)p->cl.cellEnd.ptr, p->cl.validCell, N, p->cl.grid, Lb, p->shear, p->rcut * p->rcut, make_view(p), d_Mv);
+  p->lastProduct = 1;
   UH_CHECK(hipGetLastError());
   return 0;
 }
@@ -1364,9 +1371,12 @@ static int pse_lanczos_fused(void *ctx, LanczosFusedArgs *a, int n, void *stream
                        (const float2 *)p->recB.ptr, (const int2 *)p->pairRange.ptr, N, *a, (const float *)p->riderFs.ptr,
                        (float *)p->riderMFs.ptr);
     p->riderLaunched = true;
-  } else
+    p->lastProduct = 6;
+  } else {
     hipLaunchKernelGGL(k_pse_near_pairs_lanczos<false>, dim3(nb), dim3(kNearBlock), 0, st, (const float4 *)p->recA.ptr,
                        (const float2 *)p->recB.ptr, (const int2 *)p->pairRange.ptr, N, *a, (const float *)nullptr, (float *)nullptr);
+    if (!(p->riderArmed && p->riderLaunched)) p->lastProduct = 5;   // (a solve whose first product carried the rider keeps saying 6)
+  }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1596,6 +1606,13 @@ int uammd_pse_near_pair_records(uammd_pse_near *h, long long *records, long long
 
 // diagnostics of the kept candidate lists (option "list_skin_percent"): {list builds from scratch, record builds from a kept list, builds
 // repeated because the displacement bound was broken, 1 while the mechanism is on for the handle}
+// diagnostics: the product kernel the handle launched last (PSENear::lastProduct)
+int uammd_pse_near_last_product(uammd_pse_near *h, int *kind) {
+  if (!h || !kind) { set_last_error("uammd_pse_near_last_product: null argument"); return -1; }
+  *kind = reinterpret_cast<const PSENear *>(h)->lastProduct;
+  return 0;
+}
+
 int uammd_pse_near_list_stats(uammd_pse_near *h, long long out[4]) {
   if (!h || !out) { set_last_error("uammd_pse_near_list_stats: null argument"); return -1; }
   const PSENear *p = reinterpret_cast<const PSENear *>(h);
