@@ -553,6 +553,18 @@ int uammd_fcm_fft_probe(const int cells[3], int mode, int target, float *d_grid,
 /* "atomic_spread" = 1 forces the one-wave-per-particle atomic spread/gather instead of the tile-owned kernels;
  * "tile_gather" = 1 selects the LDS-staged gather (supports <= 6; slower than the default at 24 particles per tile) */
 int uammd_fcm_set_option(uammd_fcm *h, const char *name, int value);
+/* diagnostics, host-side bookkeeping only: how the last solve on this handle got its stencils (out[0]) and what the update of the last
+ * uammd_fcm_step_euler_maruyama did for the next solve (out[1]; UAMMD_FCM_UPDATE_NO_STEP when the last call was a plain solve) */
+#define UAMMD_FCM_PREP_NONE 0            /* no solve yet, or the atomic spread: nothing is prepared */
+#define UAMMD_FCM_PREP_SORTED_FRESH 1    /* k_fcm_bin_count -> k_fcm_tile_scan -> k_fcm_prepare */
+#define UAMMD_FCM_PREP_SORTED_CLAIMED 2  /* ... from the binning that the previous step's k_fcm_update_bin left */
+#define UAMMD_FCM_PREP_SLOTS_CLAIMED 3   /* the slot layout that the previous step's k_fcm_step_prep left */
+#define UAMMD_FCM_PREP_SLOTS_SELF 4      /* the slot layout prepared on the spot from the entry order of an earlier solve */
+#define UAMMD_FCM_UPDATE_NO_STEP 0
+#define UAMMD_FCM_UPDATE_STEP_PREP 1     /* k_fcm_step_prep: the next solve's slot layout */
+#define UAMMD_FCM_UPDATE_BIN 2           /* k_fcm_update_bin that also bins the positions it writes */
+#define UAMMD_FCM_UPDATE_PLAIN 3         /* k_fcm_update_bin without binning */
+int uammd_fcm_last_preparation(uammd_fcm *h, int out[2]);
 
 /* Torques and rotation (FCM_impl.cuh:306-358, :590-649; FCM_kernels.cuh:60-80; BDHI_FCM.cu:67-92).  The torque window is
  * GaussianTorque(width = a/(6 sqrt(pi))^(1/3), h, tolerance); torques are spread with it, half their curl is added to the

@@ -5,7 +5,9 @@ not defined by the reference either — so grids/velocities are compared with |d
 (FCM velocities <= 1e-5 relative L2).  The integer stencil decisions (cell, even-support
 shift) are compared exactly through the set of touched nodes.
 """
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -746,6 +748,78 @@ def test_fcm_step_random_call_sequences(hip, seed, wait):
     # (rounding level per step; the few particles that sit on a cell centre to within rounding may differ by the kernel's tolerance, as in
     # test_fcm_step_slot_layout)
     assert (d > 4e-6 * scale * max(steps, 1) ** 0.5 + 1e-5).sum() <= 5 and d.max() <= 5e-3, (float(d.max()), int((d > 1e-4).sum()))
+
+
+PREPARATION_TRACE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fcm_preparation_trace.json")
+
+
+def run_preparation_script(hip, setup, calls, tuned):
+    """Plays the call list of tests/golden/fcm_preparation_trace.json on a fresh handle, waiting for the device after every call (the
+    handle then reads the device's reports at once, so its decisions do not depend on timing).  tuned: the script's options apply;
+    otherwise the slot layout and the binning ahead are off throughout.  Returns the (preparation, update) pair after every solve or step
+    and the final position arrays."""
+    cells, L, cap, dt = setup["cells"], float(setup["L"]), int(setup["capacity"]), float(setup["dt"])
+    k, a_eff = hip.Kernels.Gaussian(1.0, setup["tolerance"])
+    fcm = hip.BDHI.FCM_impl(hip.Box(L), cells, k, setup["viscosity"], 5, a_eff)
+    if tuned:
+        fcm.set_option("slot_refresh", setup["slot_refresh"])
+    else:
+        fcm.set_option("slots", 0)
+        fcm.set_option("bin_ahead", 0)
+    rng = np.random.default_rng(setup["seed"])
+    p = np.zeros((cap, 4), np.float32)
+    p[:, :3] = rng.uniform(-0.5, 0.5, (cap, 3)) * L
+    # (two arrays with the same start, and a hand move of a fraction of a cell: the entries' order of one array then fits the other, and
+    # the spread's scrambled-order report, which depends on the data, stays at rest)
+    arrays = {name: torch.from_numpy(p.copy()).cuda() for name in ("A", "B")}
+    force = np.zeros((cap, 4), np.float32)
+    force[:, :3] = rng.normal(0, 1, (cap, 3))
+    df = torch.from_numpy(force).cuda()
+    streams = [torch.cuda.current_stream(), torch.cuda.Stream()]
+    trace = []
+    for c in calls:
+        if c["op"] == "option":
+            if tuned:
+                fcm.set_option(c["name"], c["value"])
+            continue
+        dp, n = arrays[c["array"]], c.get("n", 0)
+        if c["op"] == "move":
+            dp[:, :3] += c["by"]
+        else:
+            with torch.cuda.stream(streams[c.get("stream", 0)]):
+                f = df if c["force"] else None
+                if c["op"] == "step":
+                    fcm.stepEulerMaruyama(dp, f, n, 0.0, 1 / math.sqrt(dt), dt, positions_kept=c["kept"])
+                else:
+                    fcm.computeHydrodynamicDisplacements(dp, f, n, 0.0, 0.0)
+            trace.append(list(fcm.last_preparation()))
+        torch.cuda.synchronize()
+    return trace, {name: a.cpu().numpy() for name, a in arrays.items()}
+
+
+def test_fcm_preparation_trace(hip):
+    """Which of its four preparations the handle takes for every solve of a scripted sequence of 45 calls, and what every step's update
+    does, equals tests/golden/fcm_preparation_trace.json entry by entry (uammd_fcm_last_preparation).  The file was recorded once on
+    the GPU from the logic before the decisions moved into csrc/fcm_prep_state.hpp, and this test never writes it.  The rounding-level
+    comparisons below and elsewhere would also pass on a handle that quietly sorted every solve; this one would not.  The script: 32^3
+    (4 x 4 x 4 tiles, the smallest grid with all four preparations), N = 3000 (and 2000, 4000: one reallocation), slot_refresh = 3,
+    T = 0, two arrays, two streams, `slots` and `bin_ahead` off and on again.  The final positions equal those of a handle with both
+    off, by the bound of test_fcm_step_random_call_sequences."""
+    with open(PREPARATION_TRACE) as fh:
+        golden = json.load(fh)
+    setup, calls = golden["setup"], golden["calls"]
+    trace, a = run_preparation_script(hip, setup, calls, True)
+    assert len(trace) == len(golden["trace"])
+    for i, (got, want) in enumerate(zip(trace, golden["trace"])):
+        assert got == want, (i, got, want)
+    assert {t[0] for t in trace} == {1, 2, 3, 4} and {t[1] for t in trace} == {0, 1, 2, 3}   # (every preparation and every update occurs)
+    _, b = run_preparation_script(hip, setup, calls, False)
+    steps = sum(1 for c in calls if c["op"] == "step")
+    for name in ("A", "B"):
+        assert np.isfinite(a[name]).all() and np.array_equal(a[name][:, 3], b[name][:, 3])
+        d = np.abs(a[name][:, :3] - b[name][:, :3]).max(axis=1)
+        scale = np.abs(b[name][:, :3]).max()
+        assert (d > 4e-6 * scale * max(steps, 1) ** 0.5 + 1e-5).sum() <= 5 and d.max() <= 5e-3, (name, float(d.max()), int((d > 1e-4).sum()))
 
 
 def test_fcm_slot_layout_survives_a_relayout_of_the_callers_arrays(hip):

@@ -278,6 +278,16 @@ class FCM_impl:
     def set_option(self, name, value):
         check(self.lib.uammd_fcm_set_option(self.h, name.encode(), int(value)))
 
+    # uammd_fcm_last_preparation (include/uammd_hip.h, UAMMD_FCM_PREP_* and UAMMD_FCM_UPDATE_*)
+    PREP_NONE, PREP_SORTED_FRESH, PREP_SORTED_CLAIMED, PREP_SLOTS_CLAIMED, PREP_SLOTS_SELF = range(5)
+    UPDATE_NO_STEP, UPDATE_STEP_PREP, UPDATE_BIN, UPDATE_PLAIN = range(4)
+
+    def last_preparation(self):
+        """(how the last solve got its stencils, what the last step's update did): host-side bookkeeping, no device work."""
+        out = (C.c_int * 2)()
+        check(self.lib.uammd_fcm_last_preparation(self.h, out))
+        return int(out[0]), int(out[1])
+
     def seed2(self, value=None):
         if value is None:
             v = C.c_uint(0)

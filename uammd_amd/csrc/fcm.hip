@@ -18,11 +18,13 @@
 //   * all work buffers are owned by the handle; steady state allocates nothing.
 #include "ibm.hpp"
 #include "celllist.hpp"
+#include "fcm_prep_state.hpp"
 #include "rocfft_plans.hpp"
 #include "saru.hpp"
 
 #include <cmath>
 #include <memory>
+#include <type_traits>
 #include <string>
 
 namespace uammd_hip {
@@ -30,7 +32,7 @@ namespace uammd_hip {
 // PSE far field (FarField.cuh:85-119): hydrodynamic radius, Ewald splitting, kernel splitting, shear strain
 struct PseGreens { float rh, split, eta, shear; bool on; };
 
-// the tile-sorted stencil arrays of a solve (fcm_prepare_tiles)
+// the tile-sorted stencil arrays of a solve (fcm_prepare)
 struct FcmPrep {
   // all arrays below are in TILE-SORTED order (slot = tileStart[tile] + rank) except tileOf/rank
   int4 *origin;     // int4[N]: first stencil node per axis (celli - P), unwrapped; .w = original particle index
@@ -68,46 +70,24 @@ struct FCM {
   DeviceBuffer gridBuf, gridBufT, interBuf, prepOrigin, prepWeights, prepTileOf, prepRank, prepTileCount, prepTileStart, prepSorted;
   int emVelN = 0;
   DeviceBuffer emVel;              // velocities of uammd_fcm_step_euler_maruyama when the caller keeps none
-  bool emBin = true;               // uammd_fcm_step_euler_maruyama: the update kernel also bins the positions it writes for the next call
-  bool binnedPending = false;      // tileCount / tileOf / rank hold the binning of binnedPos (written by k_fcm_update_bin)
-  const void *binnedPos = nullptr;
-  int binnedN = 0;
+  FcmPrepState prep;              // which preparation each solve takes, and what the counters and the entry order hold (fcm_prep_state.hpp)
   bool useTiles = false;   // grid divisible by the tile and >= 3 tiles per dimension
   int3 ntiles{0, 0, 0};
   int3 tdim{8, 8, 8};      // tile edge per axis, 4..8 nodes: the largest divisor of the axis that holds the stencil's reach (fcm_tiles_usable)
-  int prepCapN = 0;
-  bool tileCountZero = false;       // prepTileCount holds zeros (k_fcm_tile_scan leaves it so)
   // slot layout (FcmPrep::cap > 0): uammd_fcm_step_euler_maruyama's update kernel prepares the NEXT solve completely (k_fcm_step_prep)
   DeviceBuffer prepRec, prepOvfTile, prepSlotCount;
-  bool slotsEnabled = !(getenv("UAMMD_FCM_SLOTS") && atoi(getenv("UAMMD_FCM_SLOTS")) == 0);   // option "slots" (environment: A/B runs of programs that do not set options)
-  int slotCap = 0;                  // records per tile
-  int slotParity = 0;               // which half of prepSlotCount the pending preparation counted into
-  bool slotPending = false;         // origin / weights / rec / counters hold the preparation of slotPos (k_fcm_step_prep)
-  bool slotDirty = true;            // the counters may hold anything (first use, or a pending preparation was dropped)
-  const void *slotPos = nullptr;
-  int slotN = 0;
-  int slotRefresh = 128;            // a sorted (compact) solve every so many steps: the entries' order is what keeps the gather's windows local (option "slot_refresh")
-  bool lastSolveSlots = false;      // the solve that has just run read the slot layout
-  int orderN = 0;                   // origin[0 .. orderN).w is a permutation of the particles (entry -> particle) left by an earlier solve of orderN particles
-  int slotSteps = 0;                // slot-layout steps since the last sorted solve (the entries' order is refreshed every kSlotRefresh)
   int *slotFlagHost = nullptr, *slotFlagDev = nullptr;  // mapped: the spread reports an overflow list that is long enough to cost time
   bool binBySlot = true;            // option "bin_by_slot": the step's update + binning pass walks the particles in the solve's tile order (k_fcm_update_bin)
-  hipStream_t prepStream = nullptr;  // ... an ordering that only holds within one stream: a call on another stream waits for this one first
-  bool prepStreamSet = false;
   bool forceAtomicSpread = false;  // test hook
   bool interGather = true;         // gather from an interleaved float4 copy of the velocity grids (k_fcm_interleave)
   int gatherPerWave = 2;           // particles per wave of k_fcm_gather_inter (1, 2, 4)
   int spreadWaves = 0;             // waves per tile of k_fcm_spread_tile: 0 = by the tiles' population (spread_waves), 2, 4
-  bool tileGather = false;         // LDS-staged gather (k_fcm_gather_tile): measured SLOWER than the global gather, off
   bool accumulate = false;         // gather adds into the output (IBM::gather semantics; PSE far field)
   int zTileLog2 = 0;               // test / tuning hook: log2 of the fused z pass's node tile (0 = default)
   bool customFFT = true;           // power-of-two grids: the five-pass LDS FFT pipeline of fcm_fft.hpp instead of rocFFT + k_fcm_kspace
   PseGreens pse{0.f, 0.f, 0.f, 0.f, false};  // PSE far field: Hasimoto-split RPY greens function instead of 1/(eta k^2)
   RealFFT fft;             // (the z-slab solver runs its own four plans through this one's info and work buffer)
   unsigned int seed2 = 0;  // the reference's `static uint seed2` (FCM_impl.cuh:517): per-handle here
-  FcmPrep halfPrep{};      // a solve queued in two halves (fcm_displacements_impl): the stencil view of the first for the second
-  int halfN = 0;
-  bool halfPending = false;
   ~FCM() {
     if (slotFlagHost) (void)hipHostFree(slotFlagHost);
   }
@@ -403,7 +383,7 @@ __global__ void __launch_bounds__(256) k_fcm_step_prep(float4 *__restrict__ pos,
   // how well the entries' order still follows the tiles (it is only an index permutation: a caller that re-lays its arrays out — a
   // sort, a compaction after migration — scrambles it without anybody noticing, and the gather's windows stop sharing cache lines:
   // 31 -> 77 us at C4).  Tile changes between consecutive entries of a wave: ~ntiles for a sorted order, ~N for a scrambled one;
-  // the host compares (fcm_prepare_best) and goes through the sorted layout again when it is the latter.
+  // the host compares (fcm_prep_inputs, FcmPrepState) and goes through the sorted layout again when it is the latter.
   // (SAMPLED: one wave in 64 counts — thousands of atomics on one address serialise in the L2: with every wave counting the kernel
   // went from 13 to ~60 us — and the host scales the count back)
   if ((blockIdx.x & 15) == 0 && threadIdx.x < 64) {
@@ -1850,68 +1830,137 @@ static int fcm_fft_inverse_x(FCM *f, float *g, float4 *inter, hipStream_t st, bo
   return 0;
 }
 
-// bins the particles by tile and fills the tile-sorted stencil origins / weights / forces (reused by spread and gather)
-static int fcm_prepare_tiles(FCM *f, const float *d_pos, const float *d_force, int N, hipStream_t st, FcmPrep *out, bool positionsKept = false) {
+// ---- the stencils of a solve: fcm.hip executes what FcmPrepState (fcm_prep_state.hpp) decides ------------------------------------------
+static_assert(kFcmPrepNone == UAMMD_FCM_PREP_NONE && kFcmPrepSortedFresh == UAMMD_FCM_PREP_SORTED_FRESH && kFcmPrepSortedClaimed == UAMMD_FCM_PREP_SORTED_CLAIMED &&
+              kFcmPrepSlotsClaimed == UAMMD_FCM_PREP_SLOTS_CLAIMED && kFcmPrepSlotsSelf == UAMMD_FCM_PREP_SLOTS_SELF, "uammd_fcm_last_preparation");
+static_assert(kFcmUpdateNoStep == UAMMD_FCM_UPDATE_NO_STEP && kFcmUpdateStepPrep == UAMMD_FCM_UPDATE_STEP_PREP && kFcmUpdateBin == UAMMD_FCM_UPDATE_BIN &&
+              kFcmUpdatePlain == UAMMD_FCM_UPDATE_PLAIN, "uammd_fcm_last_preparation");
+
+// the handle's arrays as the kernels see them: the compact (tile-sorted) layout, or the slot layout with this solve's counters in `parity`
+static FcmPrep fcm_prep_view(const FCM *f, bool slots, int parity, const float *d_force) {
   const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
   const int wstride = f->kern.support.x + f->kern.support.y + f->kern.support.z;
-  if (f->slotPending) {  // (a slot-layout preparation that nobody claimed: this call rewrites the arrays it points into)
-    f->slotPending = false;
-    f->slotDirty = true;
+  if (!slots)
+    return FcmPrep{(int4 *)f->prepOrigin.ptr, (float *)f->prepWeights.ptr, (float4 *)f->prepSorted.ptr, (int *)f->prepTileOf.ptr,
+                   (int *)f->prepRank.ptr, (int *)f->prepTileCount.ptr, (int *)f->prepTileStart.ptr, wstride, f->tdim};
+  int *counts = (int *)f->prepSlotCount.ptr;
+  return FcmPrep{(int4 *)f->prepOrigin.ptr, (float *)f->prepWeights.ptr, nullptr, nullptr, nullptr, nullptr, nullptr, wstride, f->tdim,
+                 (unsigned long long *)f->prepRec.ptr, (int *)f->prepOvfTile.ptr, f->prep.slotCapacity(), counts + (size_t)parity * (nt + 2),
+                 counts + (size_t)(parity ^ 1) * (nt + 2), f->slotFlagDev, (const float4 *)d_force};
+}
+
+// k_fcm_prepare and k_fcm_step_prep are instantiated per window kind and per lanes per particle (at 2e5 particles the chip is full with one
+// lane each): launch(kind, lanes, blocks) gets both as integral constants.  False: the window kind has no such kernel.
+template <class Launch>
+static bool fcm_dispatch_prep(int kind, int N, Launch &&launch) {
+#define UH_KIND(K)                                                                                                               \
+  case K:                                                                                                                        \
+    if (N <= kPrepLanesUpTo) launch(std::integral_constant<int, K>{}, std::integral_constant<int, kPrepLanes>{}, dim3((unsigned)(((size_t)N * kPrepLanes + 255) / 256))); \
+    else launch(std::integral_constant<int, K>{}, std::integral_constant<int, 1>{}, dim3((N + 255) / 256));                     \
+    return true;
+  switch (kind) {
+    UH_KIND(kKernelGaussian) UH_KIND(kKernelPeskin3) UH_KIND(kKernelPeskin4) UH_KIND(kKernelConstant) UH_KIND(kKernelBarnettMagland) UH_KIND(kKernelSixPoint)
   }
-  f->slotSteps = 0;  // a sorted solve: the entries' order is fresh
-  if (f->prepCapN < N) {
+#undef UH_KIND
+  set_last_error("fcm: window kind %d has no spreading kernel", kind);
+  return false;
+}
+
+// what the state's rules read from outside: the two reports that the spread of a slot-layout solve leaves in host-mapped memory (read
+// without a wait: a solve or two late is soon enough) and whether the slot layout's records fit
+static FcmPrepInputs fcm_prep_inputs(FCM *f, const float *d_pos, const float *d_force, int N, hipStream_t st, bool positionsKept, bool tiles) {
+  FcmPrepInputs c{(const void *)d_pos, N, (const void *)st, positionsKept, d_force != nullptr, tiles, false, false, false, 0, false};
+  if (!tiles) return c;
+  const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
+  if (f->prep.slots && !f->slotFlagHost) {
+    if (hipHostMalloc((void **)&f->slotFlagHost, 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); f->slotFlagHost = nullptr; f->prep.slots = false; }
+    else {
+      f->slotFlagHost[0] = 0;
+      f->slotFlagHost[1] = 0;
+      if (hipHostGetDevicePointer((void **)&f->slotFlagDev, f->slotFlagHost, 0) != hipSuccess) { (void)hipGetLastError(); f->prep.slots = false; }
+    }
+  }
+  if (f->slotFlagHost) {
+    c.overflowReport = ((volatile int *)f->slotFlagHost)[0] != 0;
+    c.scrambledReport = 64L * ((volatile int *)f->slotFlagHost)[1] > (long)std::max(4 * nt, N / 4);   // (tile changes along the entries; one wave in 64 counted)
+  }
+  c.slotCap = std::max(32, ((int)(3.0 * ((double)N / nt)) + 16 + 7) & ~7);
+  const size_t recBytes = sizeof(unsigned long long) * ((size_t)nt * c.slotCap + (size_t)N);
+  c.slotFits = recBytes <= ((size_t)1 << 30) && N < (1 << 21);
+  c.slotBuffersHold = f->prepRec.cap >= recBytes && f->prepOvfTile.cap >= sizeof(int) * (size_t)N && f->prepSlotCount.cap >= sizeof(int) * 2 * ((size_t)nt + 2);
+  return c;
+}
+
+// k_fcm_step_prep as planned: for a solve on the spot (v = nullptr), or as the update kernel of a step
+static int fcm_step_prep_run(FCM *f, const FcmStepPrepPlan &p, const FcmPrepInputs &c, float *d_pos, const float *v, float dt, hipStream_t st) {
+  const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z, N = c.N;
+  if (p.growSlots) {
     UH_CHECK(hipStreamSynchronize(st));
-    f->orderN = 0;
+    if (int e = f->prepRec.reserve(sizeof(unsigned long long) * ((size_t)nt * c.slotCap + (size_t)N))) return e;
+    if (int e = f->prepOvfTile.reserve(sizeof(int) * (size_t)N)) return e;
+    if (int e = f->prepSlotCount.reserve(sizeof(int) * 2 * ((size_t)nt + 2))) return e;
+  }
+  if (p.zeroSlotCounts) UH_CHECK(hipMemsetAsync(f->prepSlotCount.ptr, 0, sizeof(int) * 2 * ((size_t)nt + 2), st));
+  const FcmPrep pr = fcm_prep_view(f, true, p.parity, nullptr);   // (origin: entry -> particle from an earlier solve; rewritten entry by entry)
+  if (!fcm_dispatch_prep(f->kern.kind, N, [&](auto kind, auto lanes, dim3 blocks) {
+        hipLaunchKernelGGL((k_fcm_step_prep<decltype(kind)::value, decltype(lanes)::value>), blocks, dim3(256), 0, st, (float4 *)d_pos, v, N, dt, f->grid,
+                           f->kern, f->ntiles, pr, N);
+      })) return -3;
+  UH_CHECK(hipGetLastError());
+  return 0;
+}
+
+// asks the state before a solve and executes its plan
+static int fcm_prepare_run(FCM *f, const float *d_pos, const float *d_force, int N, hipStream_t st, bool positionsKept, bool tiles, FcmPrep *out,
+                           bool *slots) {
+  const FcmPrepInputs c = fcm_prep_inputs(f, d_pos, d_force, N, st, positionsKept, tiles);
+  const FcmSolvePlan p = f->prep.beforeSolve(c);
+  *slots = p.slots();
+  *out = FcmPrep{};
+  if (p.clearScrambled) f->slotFlagHost[1] = 0;
+  if (p.prep == kFcmPrepNone) return 0;
+  const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
+  if (p.slots()) {
+    if (p.prep == kFcmPrepSlotsSelf)
+      if (int e = fcm_step_prep_run(f, p, c, const_cast<float *>(d_pos), nullptr, 0.0f, st)) return e;
+    *out = fcm_prep_view(f, true, p.parity, d_force);
+    if (p.zeroSlotNext) UH_CHECK(hipMemsetAsync(out->slotCountNext, 0, sizeof(int) * (size_t)(nt + 2), st));
+    return 0;
+  }
+  if (p.growCompact) {
+    const int wstride = f->kern.support.x + f->kern.support.y + f->kern.support.z;
+    UH_CHECK(hipStreamSynchronize(st));
     if (int e = f->prepOrigin.reserve(sizeof(int4) * (size_t)N)) return e;
     if (int e = f->prepWeights.reserve(sizeof(float) * (size_t)wstride * N)) return e;
     if (int e = f->prepSorted.reserve(sizeof(float4) * (size_t)N)) return e;
     if (int e = f->prepTileOf.reserve(sizeof(int) * (size_t)N)) return e;
     if (int e = f->prepRank.reserve(sizeof(int) * (size_t)N)) return e;
     if (int e = f->prepTileCount.reserve(sizeof(int) * (size_t)nt)) return e;
-    f->tileCountZero = false;
     if (int e = f->prepTileStart.reserve(sizeof(int) * ((size_t)nt + 1))) return e;
-    f->prepCapN = N;
   }
-  FcmPrep pr{(int4 *)f->prepOrigin.ptr, (float *)f->prepWeights.ptr, (float4 *)f->prepSorted.ptr,
-             (int *)f->prepTileOf.ptr, (int *)f->prepRank.ptr, (int *)f->prepTileCount.ptr,
-             (int *)f->prepTileStart.ptr, wstride, f->tdim};
-  if (f->prepStreamSet && f->prepStream != st) {  // the handle's buffers (and the zeroed counters) are ordered by the stream of the last call
-    UH_CHECK(hipStreamSynchronize(f->prepStream));
-    f->tileCountZero = false;
-  }
-  // the previous uammd_fcm_step_euler_maruyama binned the positions it wrote (k_fcm_update_bin): its counts are in tileCount, the tiles
-  // and ranks in tileOf / rank.  Used when the caller vouches that the array is untouched and it is the same array; dropped otherwise.
-  const bool binned = f->binnedPending && positionsKept && f->binnedPos == (const void *)d_pos && f->binnedN == N && f->prepStream == st;
-  if (f->binnedPending && !binned) f->tileCountZero = false;
-  f->binnedPending = false;
-  f->prepStream = st;
-  f->prepStreamSet = true;
-  if (!f->tileCountZero) {  // first use of the buffer; afterwards k_fcm_tile_scan hands the counters back zeroed
-    UH_CHECK(hipMemsetAsync(pr.tileCount, 0, sizeof(int) * (size_t)nt, st));
-    f->tileCountZero = true;
-  }
-  if (!binned)
+  if (p.haveWait) UH_CHECK(hipStreamSynchronize((hipStream_t)const_cast<void *>(p.waitFor)));
+  const FcmPrep pr = fcm_prep_view(f, false, 0, nullptr);
+  if (p.zeroTileCount) UH_CHECK(hipMemsetAsync(pr.tileCount, 0, sizeof(int) * (size_t)nt, st));
+  if (p.prep == kFcmPrepSortedFresh)
     hipLaunchKernelGGL(k_fcm_bin_count, dim3((N + 255) / 256), dim3(256), 0, st, (const float4 *)d_pos, N, f->grid,
                        f->ntiles, pr, f->kern.support);
   hipLaunchKernelGGL(k_fcm_tile_scan, dim3(1), dim3(1024), 0, st, pr.tileCount, nt, pr.tileStart);
-#define UH_PREPARE(K)                                                                                          \
-  case K:                                                                                                      \
-    if (N <= kPrepLanesUpTo)                                                                                   \
-      hipLaunchKernelGGL((k_fcm_prepare<K, kPrepLanes>), dim3((N * kPrepLanes + 255) / 256), dim3(256), 0, st, (const float4 *)d_pos, \
-                         (const float4 *)d_force, N, f->grid, f->kern, pr);                                    \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_fcm_prepare<K, 1>), dim3((N + 255) / 256), dim3(256), 0, st, (const float4 *)d_pos, \
-                         (const float4 *)d_force, N, f->grid, f->kern, pr);                                    \
-    break;
-  switch (f->kern.kind) {
-    UH_PREPARE(kKernelGaussian) UH_PREPARE(kKernelPeskin3) UH_PREPARE(kKernelPeskin4) UH_PREPARE(kKernelConstant)
-    UH_PREPARE(kKernelBarnettMagland) UH_PREPARE(kKernelSixPoint)
-    default: set_last_error("fcm: window kind %d has no spreading kernel", f->kern.kind); return -3;
-  }
-#undef UH_PREPARE
-  f->orderN = N;  // (origin[slot].w = the particle of compact slot `slot`: the entry order of the slot layout)
+  if (!fcm_dispatch_prep(f->kern.kind, N, [&](auto kind, auto lanes, dim3 blocks) {
+        hipLaunchKernelGGL((k_fcm_prepare<decltype(kind)::value, decltype(lanes)::value>), blocks, dim3(256), 0, st, (const float4 *)d_pos,
+                           (const float4 *)d_force, N, f->grid, f->kern, pr);
+      })) return -3;
   *out = pr;
   return 0;
+}
+
+// The stencils of a solve, the cheapest way that applies (FcmPrepState::beforeSolve).  *slots says which layout `out` describes (the
+// spread kernel's template argument).  The state records its plan as taken: when a reserve or a launch fails, it is told so, and the
+// caller who frees memory and calls again gets a fresh attempt.
+static int fcm_prepare(FCM *f, const float *d_pos, const float *d_force, int N, hipStream_t st, bool positionsKept, bool tiles, FcmPrep *out,
+                       bool *slots) {
+  const int e = fcm_prepare_run(f, d_pos, d_force, N, st, positionsKept, tiles, out, slots);
+  if (e) f->prep.planNotExecuted();
+  return e;
 }
 
 // tile-owned spreading is possible when the grid is a whole number (>= 3) of tiles per axis and a stencil only
@@ -2107,56 +2156,6 @@ int uammd_fcm_fft_probe(const int cells[3], int mode, int target, float *d_grid,
 // half: 0 = the whole solve; 1 = its first half (binning, stencils, spreading, the forward x / y transforms), 2 = the second (z transform,
 // operator and noise, inverse transforms, gather) of a solve whose first half was queued on the same stream with the same arguments —
 // for a caller with other work to queue in between (uammd_pse_far_displacements_half)
-// The stencils of a solve, the cheapest way that applies: (1) the previous step's update kernel prepared it (k_fcm_step_prep) and the
-// caller vouches that the array is untouched; (2) nobody prepared it but an earlier solve of these N particles left an entry order:
-// the same kernel without the update, ONE launch instead of k_fcm_bin_count -> k_fcm_tile_scan -> k_fcm_prepare (every slotRefresh-th
-// solve goes through the sorted layout again: the entries' order is what keeps the gather's windows local); (3) the sorted layout.
-// *slots says which layout `pr` describes (the spread kernel's template argument).
-static bool fcm_step_prep_launch(FCM *f, float *d_pos, const float *v, int N, float dt, hipStream_t st, int *rc);
-// the spread of the last slot-layout solve reported how many tile changes its entry sequence had (FcmPrep::slotFlag[1]; read without
-// a wait: a solve or two late is soon enough)
-static bool fcm_entries_scrambled(FCM *f, int N) {
-  if (!f->slotFlagHost) return false;
-  const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
-  const long changes = 64L * ((volatile int *)f->slotFlagHost)[1];   // (one wave in 64 counted)
-  if (changes <= (long)std::max(4 * nt, N / 4)) return false;
-  f->slotFlagHost[1] = 0;
-  return true;
-}
-static int fcm_prepare_best(FCM *f, const float *d_pos, const float *d_force, int N, hipStream_t st, bool positionsKept, FcmPrep *out,
-                            bool *slotsOut) {
-  bool slots = f->slotPending && !f->tileGather && positionsKept && f->slotPos == (const void *)d_pos && f->slotN == N && f->prepStreamSet &&
-               f->prepStream == st;
-  // (a pending preparation is used whatever its order: it is correct, and the step's update kernel looks at the order itself)
-  const bool scrambled = !slots && fcm_entries_scrambled(f, N);
-  if (f->slotPending && !slots) f->slotDirty = true;  // dropped: its counters are garbage now
-  f->slotPending = false;
-  if (!slots && !scrambled && f->slotsEnabled && !f->tileGather && f->orderN == N && f->prepStreamSet && f->prepStream == st) {  // (k_fcm_gather_tile walks compact tile ranges)
-    int rc = 0;
-    if (fcm_step_prep_launch(f, const_cast<float *>(d_pos), nullptr, N, 0.0f, st, &rc)) {
-      if (rc) return rc;
-      slots = true;
-      f->slotPending = false;
-    }
-  }
-  *slotsOut = slots;
-  if (!slots) return fcm_prepare_tiles(f, d_pos, d_force, N, st, out, positionsKept);
-  const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
-  int *counts = (int *)f->prepSlotCount.ptr;
-  *out = FcmPrep{(int4 *)f->prepOrigin.ptr, (float *)f->prepWeights.ptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 f->kern.support.x + f->kern.support.y + f->kern.support.z, f->tdim, (unsigned long long *)f->prepRec.ptr,
-                 (int *)f->prepOvfTile.ptr, f->slotCap, counts + (size_t)f->slotParity * (nt + 2),
-                 counts + (size_t)(f->slotParity ^ 1) * (nt + 2), f->slotFlagDev, (const float4 *)d_force};
-  // (a compact binning that k_fcm_update_bin left pending — the step fell back to it, e.g. because the entries' order was reported scrambled —
-  // is dropped here: its counts are still in tileCount, which the next sorted solve must not take for zeroed.  Found in round 6 as a memory
-  // fault of test_fcm_step_bins_ahead run on its own: ranks from stale counts sent k_fcm_prepare's rows past the arrays)
-  if (f->binnedPending) f->tileCountZero = false;
-  f->binnedPending = false;
-  // (no forces: no spread to hand the other parity's counters back zeroed)
-  if (!d_force) UH_CHECK(hipMemsetAsync(out->slotCountNext, 0, sizeof(int) * (size_t)(nt + 2), st));
-  return 0;
-}
-
 static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float *d_force, int N, float temperature,
                                   float prefactor, float *d_linearVelocity, int stage, void *stream, bool positionsKept, int half = 0) {
   if (!h) { set_last_error("uammd_fcm_displacements: null argument"); return -1; }
@@ -2173,15 +2172,10 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
   const bool custom = stage == 0 && fcm_custom_fft_usable(f);  // (stage 1 exports the Fourier grid, which the fused z pass never stores)
   FcmPrep pr{};
   bool slots = false;
-  if (half != 2) f->halfPending = false;   // (a first half whose second never came is forgotten by the next solve)
-  if (half == 2) {
-    if (!f->halfPending || f->halfN != N) { set_last_error("uammd_fcm: the second half of a solve without its first"); return -1; }
-    pr = f->halfPrep;
-    f->halfPending = false;
-  } else if (tiles) {
-    if (int e = fcm_prepare_best(f, d_pos, d_force, N, st, positionsKept, &pr, &slots)) return e;
-  }
-  if (half != 2) f->lastSolveSlots = slots;  // (the second half of a solve reads what the first half prepared)
+  if (half == 2) {  // (the second half of a solve reads what the first half prepared)
+    if (!f->prep.takeSecondHalf(N)) { set_last_error("uammd_fcm: the second half of a solve without its first"); return -1; }
+    if (tiles) pr = fcm_prep_view(f, f->prep.lastSolveReadSlots(), f->prep.lastSlotParity(), d_force);
+  } else if (int e = fcm_prepare(f, d_pos, d_force, N, st, positionsKept, tiles, &pr, &slots)) return e;
   if (d_force && half != 2) {
     if (tiles) {
       const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
@@ -2223,9 +2217,7 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
     else if (int e = f->fft.forward(g)) return e;
   }
   if (half == 1) {
-    f->halfPrep = pr;
-    f->halfN = N;
-    f->halfPending = true;
+    f->prep.firstHalfQueued(N);
     UH_CHECK(hipGetLastError());
     return 0;
   }
@@ -2250,10 +2242,10 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
     if (stage == 1) { UH_CHECK(hipGetLastError()); return 0; }
     if (int e = f->fft.inverse(g)) return e;
   }
-  const bool interPath = tiles && f->interGather && !(tiles && (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6) && f->tileGather);
+  const bool interPath = tiles && f->interGather && !(tiles && (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6) && f->prep.tileGather);
   if (custom && !interPath) { if (int e = fcm_fft_inverse_x(f, g, nullptr, st)) return e; }
   const bool smallSupport = f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6;
-  if (tiles && smallSupport && f->tileGather)
+  if (tiles && smallSupport && f->prep.tileGather)
     hipLaunchKernelGGL(k_fcm_gather_tile, dim3(f->ntiles.x * f->ntiles.y * f->ntiles.z), bp, 0, st, d_linearVelocity,
                        (const float *)g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles,
                        f->grid.cellVolume, dsx, dsxy, pr, f->accumulate);
@@ -2283,77 +2275,25 @@ int uammd_fcm_displacements_staged(uammd_fcm *h, const float *d_pos, const float
   return fcm_displacements_impl(h, d_pos, d_force, N, temperature, prefactor, d_linearVelocity, stage, stream, false);
 }
 
-// The slot layout's preparation as the step's update kernel (k_fcm_step_prep).  Returns false when the slot layout is not to be used for
-// the next solve (then the caller runs the compact layout's update kernel); true with *rc set otherwise.
-static bool fcm_step_prep_launch(FCM *f, float *d_pos, const float *v, int N, float dt, hipStream_t st, int *rc) {
-  *rc = 0;
-  if (f->slotFlagHost && f->slotFlagHost[0]) {  // the spread met a long overflow list: this system is too clustered for fixed capacities
-    f->slotsEnabled = false;
-    return false;
-  }
-  if (f->slotSteps >= f->slotRefresh) { f->slotSteps = 0; return false; }
-  if (v && fcm_entries_scrambled(f, N)) return false;   // (the step's update kernel: the compact layout's, so that the next solve sorts)
-  const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
-  const double mean = (double)N / nt;
-  const int cap = std::max(32, ((int)(3.0 * mean) + 16 + 7) & ~7);
-  const size_t recBytes = sizeof(unsigned long long) * ((size_t)nt * cap + (size_t)N);
-  if (recBytes > ((size_t)1 << 30) || N >= (1 << 21)) return false;  // (a record holds entry and particle in 21 bits each)
-  auto fail = [&](int e) { *rc = e; return true; };
-  if (!f->slotFlagHost) {
-    if (hipHostMalloc((void **)&f->slotFlagHost, 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); f->slotsEnabled = false; return false; }
-    f->slotFlagHost[0] = 0;
-    f->slotFlagHost[1] = 0;
-    if (hipHostGetDevicePointer((void **)&f->slotFlagDev, f->slotFlagHost, 0) != hipSuccess) { (void)hipGetLastError(); f->slotsEnabled = false; return false; }
-  }
-  if (f->prepRec.cap < recBytes || f->prepOvfTile.cap < sizeof(int) * (size_t)N || f->slotCap != cap || f->prepSlotCount.cap < sizeof(int) * 2 * ((size_t)nt + 2)) {
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(-1);
-    if (int e = f->prepRec.reserve(recBytes)) return fail(e);
-    if (int e = f->prepOvfTile.reserve(sizeof(int) * (size_t)N)) return fail(e);
-    if (int e = f->prepSlotCount.reserve(sizeof(int) * 2 * ((size_t)nt + 2))) return fail(e);
-    f->slotCap = cap;
-    f->slotDirty = true;
-  }
-  int *counts = (int *)f->prepSlotCount.ptr;
-  int parity;
-  if (f->lastSolveSlots && !f->slotDirty) parity = f->slotParity ^ 1;  // (the spread of the solve above zeroed these)
-  else {
-    if (hipMemsetAsync(counts, 0, sizeof(int) * 2 * ((size_t)nt + 2), st) != hipSuccess) return fail(-1);
-    f->slotDirty = false;
-    parity = 0;
-  }
+// the update of a step: pos += v dt by the kernel that FcmPrepState::afterStepSolve names, which also prepares the next solve
+static int fcm_step_update(FCM *f, float *d_pos, const float *d_force, int N, const float *v, float dt, hipStream_t st) {
+  const bool tiles = f->useTiles && !f->forceAtomicSpread;
+  const FcmPrepInputs c = fcm_prep_inputs(f, d_pos, d_force, N, st, false, tiles);
+  const FcmUpdatePlan u = f->prep.afterStepSolve(c);
+  if (u.clearScrambled) f->slotFlagHost[1] = 0;
+  if (u.update == kFcmUpdateStepPrep) return fcm_step_prep_run(f, u, c, d_pos, v, dt, st);
+  const bool bin = u.update == kFcmUpdateBin;
   FcmPrep pr{};
-  pr.origin = (int4 *)f->prepOrigin.ptr;   // entry -> particle from the solve above; rewritten entry by entry
-  pr.weights = (float *)f->prepWeights.ptr;
-  pr.wstride = f->kern.support.x + f->kern.support.y + f->kern.support.z;
-  pr.tdim = f->tdim;
-  pr.rec = (unsigned long long *)f->prepRec.ptr;
-  pr.ovfTile = (int *)f->prepOvfTile.ptr;
-  pr.cap = cap;
-  pr.slotCount = counts + (size_t)parity * (nt + 2);
-#define UH_STEP_PREP(K)                                                                                                                        \
-  case K:                                                                                                                                      \
-    if (N <= kPrepLanesUpTo)                                                                                                                   \
-      hipLaunchKernelGGL((k_fcm_step_prep<K, kPrepLanes>), dim3((unsigned)(((size_t)N * kPrepLanes + 255) / 256)), dim3(256), 0, st, (float4 *)d_pos, v, N, \
-                         dt, f->grid, f->kern, f->ntiles, pr, N);                                                                              \
-    else                                                                                                                                       \
-      hipLaunchKernelGGL((k_fcm_step_prep<K, 1>), dim3((N + 255) / 256), dim3(256), 0, st, (float4 *)d_pos, v, N, dt, f->grid, f->kern,         \
-                         f->ntiles, pr, N);                                                                                                    \
-    break;
-  switch (f->kern.kind) {
-    UH_STEP_PREP(kKernelGaussian) UH_STEP_PREP(kKernelPeskin3) UH_STEP_PREP(kKernelPeskin4) UH_STEP_PREP(kKernelConstant)
-    UH_STEP_PREP(kKernelBarnettMagland) UH_STEP_PREP(kKernelSixPoint)
-    default: return false;
+  if (bin) {
+    pr.tileOf = (int *)f->prepTileOf.ptr; pr.rank = (int *)f->prepRank.ptr; pr.tileCount = (int *)f->prepTileCount.ptr;
+    pr.origin = (int4 *)f->prepOrigin.ptr;   // (the stencils of the solve above: slot -> particle)
+    pr.tdim = f->tdim;
+    if (u.zeroTileCount) UH_CHECK(hipMemsetAsync(pr.tileCount, 0, sizeof(int) * (size_t)(f->ntiles.x * f->ntiles.y * f->ntiles.z), st));
   }
-#undef UH_STEP_PREP
-  if (hipGetLastError() != hipSuccess) return fail(-1);
-  f->slotParity = parity;
-  f->slotPending = true;
-  f->slotPos = (const void *)d_pos;
-  f->slotN = N;
-  f->slotSteps++;
-  if (f->binnedPending) f->tileCountZero = false;   // (see fcm_prepare_best)
-  f->binnedPending = false;
-  return true;
+  hipLaunchKernelGGL(k_fcm_update_bin, dim3((N + 255) / 256), dim3(256), 0, st, (float4 *)d_pos, (const float *)v, N, dt, f->grid, f->ntiles,
+                     pr, bin, bin && f->binBySlot, f->kern.support);
+  UH_CHECK(hipGetLastError());
+  return 0;
 }
 
 // BDHI::FCMIntegrator::forwardTime without torques (BDHI_FCM.cu:67-119): v = M F + sqrt(2 T / dt) dW as uammd_fcm_displacements, then
@@ -2376,38 +2316,25 @@ int uammd_fcm_step_euler_maruyama(uammd_fcm *h, float *d_pos, const float *d_for
   }
   if (int e = fcm_displacements_impl(h, d_pos, d_force, N, temperature, prefactor, v, 0, stream, (flags & UAMMD_FCM_STEP_POSITIONS_KEPT) != 0))
     return e;
-  const bool tiles = f->useTiles && !f->forceAtomicSpread;
-  const bool bin = tiles && f->emBin && f->prepCapN >= N;  // (the tile scan of the solve above left the counters at zero)
-  if (bin && f->slotsEnabled) {
-    int rc = 0;
-    if (fcm_step_prep_launch(f, d_pos, v, N, dt, st, &rc)) return rc;  // (launched, or failed: done either way)
-  }
-  FcmPrep pr{};
-  if (bin) {
-    pr.tileOf = (int *)f->prepTileOf.ptr; pr.rank = (int *)f->prepRank.ptr; pr.tileCount = (int *)f->prepTileCount.ptr;
-    pr.origin = (int4 *)f->prepOrigin.ptr;   // (the stencils of the solve above: slot -> particle)
-    pr.tdim = f->tdim;
-    // the binning counts on top of tileCount: zero after a sorted solve's tile scan, but NOT after a slot-layout solve that dropped an
-    // earlier unclaimed binning (fcm_prepare_best) — then they are zeroed here.  (Round 6, found by tests/test_gpu_ibm_fcm.py::
-    // test_fcm_step_random_call_sequences: ranks on top of stale counts, then a sorted solve that claimed them: wrong stencil rows.)
-    if (!f->tileCountZero) {
-      UH_CHECK(hipMemsetAsync(pr.tileCount, 0, sizeof(int) * (size_t)(f->ntiles.x * f->ntiles.y * f->ntiles.z), st));
-      f->tileCountZero = true;
-    }
-  }
-  hipLaunchKernelGGL(k_fcm_update_bin, dim3((N + 255) / 256), dim3(256), 0, st, (float4 *)d_pos, (const float *)v, N, dt, f->grid, f->ntiles,
-                     pr, bin, bin && f->binBySlot, f->kern.support);
-  UH_CHECK(hipGetLastError());
-  if (bin) { f->binnedPending = true; f->binnedPos = (const void *)d_pos; f->binnedN = N; }
+  const int e = fcm_step_update(f, d_pos, d_force, N, v, dt, st);
+  if (e) f->prep.planNotExecuted();
+  return e;
+}
+
+int uammd_fcm_last_preparation(uammd_fcm *h, int out[2]) {
+  if (!h || !out) { set_last_error("uammd_fcm_last_preparation: null argument"); return -1; }
+  const FCM *f = reinterpret_cast<const FCM *>(h);
+  out[0] = f->prep.lastPreparation();
+  out[1] = f->prep.lastUpdate();
   return 0;
 }
 
 int uammd_fcm_set_option(uammd_fcm *h, const char *name, int value) {
   if (!h || !name) { set_last_error("uammd_fcm_set_option: null argument"); return -1; }
   if (std::string(name) == "atomic_spread") { reinterpret_cast<FCM *>(h)->forceAtomicSpread = value != 0; return 0; }
-  if (std::string(name) == "bin_ahead") { reinterpret_cast<FCM *>(h)->emBin = value != 0; return 0; }
-  if (std::string(name) == "slot_refresh" && value >= 1) { reinterpret_cast<FCM *>(h)->slotRefresh = value; return 0; }
-  if (std::string(name) == "slots") { reinterpret_cast<FCM *>(h)->slotsEnabled = value != 0; return 0; }
+  if (std::string(name) == "bin_ahead") { reinterpret_cast<FCM *>(h)->prep.binAhead = value != 0; return 0; }
+  if (std::string(name) == "slot_refresh" && value >= 1) { reinterpret_cast<FCM *>(h)->prep.slotRefresh = value; return 0; }
+  if (std::string(name) == "slots") { reinterpret_cast<FCM *>(h)->prep.slots = value != 0; return 0; }
   if (std::string(name) == "bin_by_slot") { reinterpret_cast<FCM *>(h)->binBySlot = value != 0; return 0; }
   if (std::string(name) == "spread_waves") { reinterpret_cast<FCM *>(h)->spreadWaves = value; return 0; }
   if (std::string(name) == "gather_per_wave") { reinterpret_cast<FCM *>(h)->gatherPerWave = value; return 0; }
@@ -2417,7 +2344,7 @@ int uammd_fcm_set_option(uammd_fcm *h, const char *name, int value) {
     FCM *f = reinterpret_cast<FCM *>(h);
     const bool fits = f->tdim.x % 2 == 0 && f->tdim.x + f->kern.support.x - 1 <= 16 && f->tdim.y + f->kern.support.y - 1 <= 16 &&
                       f->tdim.z + f->kern.support.z - 1 <= 16;
-    f->tileGather = value != 0 && fits;
+    f->prep.tileGather = value != 0 && fits;
     return 0;
   }
   if (std::string(name) == "interleaved_gather") { reinterpret_cast<FCM *>(h)->interGather = value != 0; return 0; }
@@ -2505,10 +2432,9 @@ int uammd_fcm_slab_spread(uammd_fcm_slab *h, const float *d_posLocal, const floa
   if (N <= 0 || !d_force || !tiles) UH_CHECK(hipMemsetAsync(d_grid, 0, sizeof(float) * total, st));
   if (N <= 0) return 0;
   FcmPrep pr{};
+  bool slots = false;
+  if (int e = fcm_prepare(f, d_posLocal, d_force, N, st, false, tiles, &pr, &slots)) return e;
   if (tiles) {
-    bool slots = false;
-    if (int e = fcm_prepare_best(f, d_posLocal, d_force, N, st, false, &pr, &slots)) return e;
-    f->lastSolveSlots = slots;
     if (d_force) {
       const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
       const int ww = spread_weight_words(N, f->ntiles, f->kern.support, f->tdim);
@@ -2542,11 +2468,9 @@ int uammd_fcm_slab_gather(uammd_fcm_slab *h, const float *d_posLocal, int N, con
   const FastDiv dsx = make_fastdiv(f->kern.support.x), dsxy = make_fastdiv(f->kern.support.x * f->kern.support.y);
   const bool tiles = f->useTiles && !f->forceAtomicSpread;
   if (tiles) {
-    if (f->prepCapN < N) { set_last_error("uammd_fcm_slab_gather: call uammd_fcm_slab_spread with these positions first"); return -3; }
-    FcmPrep pr{(int4 *)f->prepOrigin.ptr, (float *)f->prepWeights.ptr, (float4 *)f->prepSorted.ptr,
-               (int *)f->prepTileOf.ptr, (int *)f->prepRank.ptr, (int *)f->prepTileCount.ptr,
-               (int *)f->prepTileStart.ptr, f->kern.support.x + f->kern.support.y + f->kern.support.z, f->tdim};
-    if (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6 && f->tileGather)
+    if (f->prep.compactCapacity() < N) { set_last_error("uammd_fcm_slab_gather: call uammd_fcm_slab_spread with these positions first"); return -3; }
+    const FcmPrep pr = fcm_prep_view(f, false, 0, nullptr);
+    if (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6 && f->prep.tileGather)
       hipLaunchKernelGGL(k_fcm_gather_tile, dim3(f->ntiles.x * f->ntiles.y * f->ntiles.z), dim3(256), 0, st, d_vel, d_grid,
                          f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles, f->grid.cellVolume, dsx, dsxy,
                          pr, f->accumulate);
@@ -2722,7 +2646,7 @@ int uammd_fcm_slab_gather_inter(uammd_fcm_slab *h, const float *d_posLocal, int 
   if (N <= 0) return 0;
   FCMSlab *s = reinterpret_cast<FCMSlab *>(h);
   FCM *f = &s->loc;
-  if (!(f->useTiles && !f->forceAtomicSpread) || f->prepCapN < N) {
+  if (!(f->useTiles && !f->forceAtomicSpread) || f->prep.compactCapacity() < N) {
     set_last_error("uammd_fcm_slab_gather_inter: needs the tile-prepared stencils of uammd_fcm_slab_spread");
     return -3;
   }
