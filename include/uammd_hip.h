@@ -677,12 +677,14 @@ int uammd_icm_set_fluid_velocity(uammd_icm *h, const float *d_in, void *stream);
 int uammd_icm_set_noise(uammd_icm *h, const float *d_random); /* test hook: 6*ncells fluid random numbers, slot-major */
 
 /* ------------------------------------------------------------------------------------------------
- * Hydro::ICM_Compressible — compressible Inertial Coupling Method, triply periodic.  Replaces
- *   ICM_Compressible_impl<DefaultWalls> / forwardTime     Integrator/Hydro/ICM_Compressible.cuh:183-452, ICM_Compressible.cu:246-257
+ * Hydro::ICM_Compressible — compressible Inertial Coupling Method, triply periodic or between two walls in z.  Replaces
+ *   ICM_Compressible_impl<Walls> / forwardTime            Integrator/Hydro/ICM_Compressible.cuh:183-452, ICM_Compressible.cu:246-257
+ *   updateGhostCellsWallsD with the built-in wall rule    ICM_Compressible/GhostCells.cuh:84-112
  *   rungeKuttaSubStepD, momentumToVelocityD, fillStochasticTensorD, spreadParticleForces, interpolateFluidVelocities
  *                                                         ICM_Compressible/{FluidSolver,SpatialDiscretization,Fluctuations,spreadInterp}.cuh
  * Density, momentum and velocity persist in the handle between steps: n^3 floats each, x fastest, no ghost cells, momentum and
- * velocity on the faces (component a of cell i at r_i + h_a/2).  Exactly one of hydrodynamicRadius > 0 / cells[0] > 0; the
+ * velocity on the faces (component a of cell i at r_i + h_a/2); with walls each field also carries its two ghost planes, which no
+ * getter but uammd_icmc_get_bottom_ghost returns.  Exactly one of hydrodynamicRadius > 0 / cells[0] > 0; the
  * reference's parameter checks fail with its messages.  seed is used as given (the callers draw one when theirs is 0).
  * Precondition: CUBIC cells (boxSize[a] / cells[a] the same on the three axes).  As in the reference, the window's scale is 1 / h_x on
  * every axis and the Laplacian and grad div are sums of differences over h_b divided by h_a; other cells are accepted and run, but
@@ -696,7 +698,25 @@ typedef struct {
   int cells[3];
   float shearViscosity, bulkViscosity, speedOfSound, temperature, dt, hydrodynamicRadius;
   unsigned int seed;
+  int walls; /* UAMMD_ICMC_WALLS_*: a zero-initialised struct has no walls */
 } uammd_icmc_parameters;
+/* Walls in z (ICM_Compressible_impl<Walls>, GhostCells.cuh; DESIGN.md §15 "Walls").  NONE: triply periodic.  BUILTIN: a wall at the
+ * bottom and one at the top of the box, each moving in its plane with a velocity (u_x, u_y) the caller sets; every field then carries
+ * two ghost planes that uammd_icmc_ghost_fill writes from the adjacent interior layer:
+ *   rho_ghost = rho_adj,  v_ghost = 2 u_wall - v_adj,  g_ghost = 2 u_wall rho_adj - g_adj,  u_wall = (u_x, u_y, 0)
+ * (the rule of the reference's test/Hydro/ICM_Compressible/walltest.cu, for both tangential components and both walls).  The particle
+ * windows do not see the walls: they wrap periodically, as the reference's do.  temperature > 0 is refused with walls. */
+enum { UAMMD_ICMC_WALLS_NONE = 0, UAMMD_ICMC_WALLS_BUILTIN = 1, UAMMD_ICMC_WALLS_EXTERNAL = 2 };
+/* EXTERNAL: the same layout, but the ghost planes are written by a kernel of the caller's.  Where BUILTIN calls uammd_icmc_ghost_fill the
+ * caller calls uammd_icmc_wall_planes_get, runs its kernel on the packed planes, and calls uammd_icmc_wall_planes_put.  The planes: per
+ * field (rho, g_x, g_y, g_z, v_x, v_y, v_z, in this order) four planes of P = (cells[0] + 2)(cells[1] + 2) floats — bottom ghost, bottom
+ * adjacent layer, top adjacent layer, top ghost — entry (i + 1) + (j + 1)(cells[0] + 2) for column (i, j), the border columns periodic
+ * images; field f, plane k at d_planes + (4 f + k) P.  The ghost planes arrive holding their periodic images in z.  _put copies the two
+ * ghost planes of every field back; writes to the adjacent planes are dropped.  uammd_icmc_set_fluid only copies the fields then: the
+ * caller fills, calls uammd_icmc_velocity_to_momentum and fills again.  uammd_icmc_ghost_fill and uammd_icmc_fluid_and_corrector fail. */
+int uammd_icmc_wall_planes_get(uammd_icmc *h, float **d_planes, void *stream);
+int uammd_icmc_wall_planes_put(uammd_icmc *h, void *stream);
+int uammd_icmc_velocity_to_momentum(uammd_icmc *h, void *stream);
 /* the parameter checks alone (host code, no GPU): 0, or -2 with the reference's message in uammd_hip_last_error() */
 int uammd_icmc_validate(const uammd_icmc_parameters *par);
 int uammd_icmc_create(const uammd_icmc_parameters *par, uammd_icmc **out, int cells[3]); /* validates; the fluid starts at rho = 1, v = 0 */
@@ -712,6 +732,20 @@ int uammd_icmc_get_collocated_velocity(uammd_icmc *h, float *d_vx, float *d_vy, 
  * The second call counts the step (the noise of step s is Saru(seed, s, cell), s from 0). */
 int uammd_icmc_predictor(uammd_icmc *h, float *d_pos, int numberParticles, void *stream);
 int uammd_icmc_fluid_and_corrector(uammd_icmc *h, float *d_pos, const float *d_force, int numberParticles, void *stream);
+/* The second call in pieces, so that a host can send the sub-step times and set the wall velocities before each ghost fill
+ * (callRungeKuttaSubStep, ICM_Compressible.cu:70-95):
+ *   fluid_begin (forcing and noise);  for s = 0, 1, 2: substage(s), ghost_fill, substage_velocity, ghost_fill;  fluid_end (corrector).
+ * uammd_icmc_fluid_and_corrector is this composition with the wall velocities held fixed.  ghost_fill uses the velocities set last
+ * (bottom and top, {u_x, u_y} each; zero after create); it acts on the level of the sub-stage under way, and on the fluid itself between
+ * steps.  Without walls ghost_fill does nothing and set_wall_velocities fails. */
+int uammd_icmc_set_wall_velocities(uammd_icmc *h, const float bottom[2], const float top[2]);
+int uammd_icmc_fluid_begin(uammd_icmc *h, const float *d_pos, const float *d_force, int numberParticles, void *stream);
+int uammd_icmc_substage(uammd_icmc *h, int s, void *stream);
+int uammd_icmc_ghost_fill(uammd_icmc *h, void *stream);
+int uammd_icmc_substage_velocity(uammd_icmc *h, void *stream);
+int uammd_icmc_fluid_end(uammd_icmc *h, float *d_pos, int numberParticles, void *stream);
+/* the bottom ghost plane (walls only): cells[0] * cells[1] floats per field, column (i, j) at i + j cells[0]; null pointers are skipped */
+int uammd_icmc_get_bottom_ghost(uammd_icmc *h, float *d_density, float *const d_v[3], float *const d_g[3], void *stream);
 /* Test hooks: the stochastic stress as float2 W[6][ncells] = {W_A, W_B} of the entries xx, yy, zz, xy, xz, yz (12 ncells floats).
  * get: the numbers the handle draws at `step`.  set: the following steps use a copy of d_noise instead of drawing (NULL: draw again). */
 int uammd_icmc_get_noise(uammd_icmc *h, unsigned int step, float *d_out, void *stream);

@@ -9,7 +9,10 @@ rounds that alternate over the four (T, particles) cases of a grid;
 per row also the share of a byte model of the three sub-stages at the copy rate of SURVEY 8d (6.29 TB/s): per cell and sub-stage 7 fields
 of time b, rho and g of time a, 3 forcing and 7 written (21 floats; 18 without particles) plus 12 noise floats when T > 0.
 
-usage: python tools/time_icm_compressible.py [--quick] [--json FILE]
+--walls adds, for every grid, the T = 0 cases between two moving walls (the built-in rule, steady wall velocities), alternating with the
+periodic ones in the same rounds: rows with "walls": true.  Noise with walls is refused, so T > 0 has no such row.
+
+usage: python tools/time_icm_compressible.py [--quick] [--walls] [--json FILE]
        rocprofv3 --kernel-trace --stats -- python tools/time_icm_compressible.py --one 64 0.01 16384 50
 """
 import json
@@ -40,7 +43,12 @@ class Fixed:
         pass
 
 
-def make(n, T, N):
+class SteadyWalls:
+    def velocities(self, t):
+        return (0.04, -0.03), (-0.02, 0.05)
+
+
+def make(n, T, N, walls=False):
     import torch
     import uammd_amd as hip
     rng = np.random.default_rng(1)
@@ -50,7 +58,8 @@ def make(n, T, N):
         p[:, :3] = rng.uniform(-0.5, 0.5, (N, 3)) * n
         pd.setPos(p)
     par = hip.Hydro.ICM_Compressible.Parameters(shearViscosity=1.0, bulkViscosity=1.0, speedOfSound=4.0, temperature=T, dt=0.05,
-                                                boxSize=[float(n)] * 3, cellDim=[n] * 3, seed=5)
+                                                boxSize=[float(n)] * 3, cellDim=[n] * 3, seed=5,
+                                                walls=SteadyWalls() if walls else None)
     icm = hip.Hydro.ICM_Compressible(pd, par)
     x = (np.arange(n) + 0.5) * 2 * np.pi / n
     rho = (1 + 0.05 * np.sin(x)[None, None, :] * np.cos(x)[None, :, None] * np.cos(x)[:, None, None]).astype(np.float32)
@@ -97,15 +106,18 @@ def main():
     quick = "--quick" in sys.argv
     out = []
     for n in ((32, 64) if quick else (32, 64, 128)):
-        cases = [(T, N) for T in (0.0, 0.01) for N in (0, 16384)]
+        cases = [(T, N, False) for T in (0.0, 0.01) for N in (0, 16384)]
+        if "--walls" in sys.argv:
+            cases += [(0.0, N, True) for N in (0, 16384)]
         icms = {c: make(n, *c) for c in cases}
         ms = {c: [] for c in cases}
         for _ in range(ROUNDS):
             for c in cases:
                 ms[c].append(timed(icms[c].forwardTime, 100.0 if quick else 300.0))
-        for (T, N) in cases:
-            med = float(np.median(ms[T, N]))
-            rec = {"grid": n, "T": T, "particles": N, "ms_forwardTime": round(med, 5), "ms_spread": round(max(ms[T, N]) - min(ms[T, N]), 5),
+        for (T, N, w) in cases:
+            med = float(np.median(ms[T, N, w]))
+            rec = {"grid": n, "T": T, "particles": N, "walls": w, "ms_forwardTime": round(med, 5),
+                   "ms_spread": round(max(ms[T, N, w]) - min(ms[T, N, w]), 5), "ms_runs": [round(x, 5) for x in ms[T, N, w]],
                    "rounds": ROUNDS, "byte_model_ms": round(model_ms(n, T, N), 5), "byte_model_share": round(model_ms(n, T, N) / med, 4)}
             print(json.dumps(rec), flush=True)
             out.append(rec)

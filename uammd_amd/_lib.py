@@ -50,7 +50,9 @@ class ICMParameters(C.Structure):
 class ICMCompressibleParameters(C.Structure):
     _fields_ = [("boxSize", C.c_float * 3), ("cells", C.c_int * 3), ("shearViscosity", C.c_float), ("bulkViscosity", C.c_float),
                 ("speedOfSound", C.c_float), ("temperature", C.c_float), ("dt", C.c_float), ("hydrodynamicRadius", C.c_float),
-                ("seed", C.c_uint)]
+                ("seed", C.c_uint), ("walls", C.c_int)]
+
+    WALLS_NONE, WALLS_BUILTIN, WALLS_EXTERNAL = 0, 1, 2
 
 
 class FIBParameters(C.Structure):
@@ -324,6 +326,16 @@ SIGNATURES = {
     "uammd_icmc_get_collocated_velocity": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "uammd_icmc_predictor": (_i, [_vp, _vp, _i, _vp]),
     "uammd_icmc_fluid_and_corrector": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_icmc_set_wall_velocities": (_i, [_vp, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 2)]),
+    "uammd_icmc_fluid_begin": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "uammd_icmc_substage": (_i, [_vp, _i, _vp]),
+    "uammd_icmc_ghost_fill": (_i, [_vp, _vp]),
+    "uammd_icmc_substage_velocity": (_i, [_vp, _vp]),
+    "uammd_icmc_fluid_end": (_i, [_vp, _vp, _i, _vp]),
+    "uammd_icmc_wall_planes_get": (_i, [_vp, C.POINTER(_vp), _vp]),
+    "uammd_icmc_wall_planes_put": (_i, [_vp, _vp]),
+    "uammd_icmc_velocity_to_momentum": (_i, [_vp, _vp]),
+    "uammd_icmc_get_bottom_ghost": (_i, [_vp, _vp, C.POINTER(_vp * 3), C.POINTER(_vp * 3), _vp]),
     "uammd_icmc_get_noise": (_i, [_vp, _u, _vp, _vp]),
     "uammd_icmc_set_noise": (_i, [_vp, _vp, _vp]),
     "uammd_fib_create": (_i, [C.POINTER(FIBParameters), C.POINTER(_vp), C.POINTER(_i3), C.POINTER(_f)]),

@@ -101,11 +101,16 @@ class ICM(Integrator):
 
 class ICM_Compressible(Integrator):
     """Hydro::ICM_Compressible(pd, par) — ICM_Compressible.cuh:183-452: inertial coupling of the particles to a fluctuating compressible
-    fluid (density and momentum on a staggered grid, explicit RK3), triply periodic.  pd may hold no particles: a fluid-only run."""
+    fluid (density and momentum on a staggered grid, explicit RK3), triply periodic or between two walls in z.  pd may hold no
+    particles: a fluid-only run."""
 
     class Parameters:
         """The reference's Parameters (:193-208).  The initial fields are callables of a position (x, y, z), evaluated on the host at
-        (cell / n + 0.5) * L as the reference does (:170-179, :385-403; also for the face-centred velocities), or arrays [nz, ny, nx]."""
+        (cell / n + 0.5) * L as the reference does (:170-179, :385-403; also for the face-centred velocities), or arrays [nz, ny, nx].
+        walls: None (triply periodic), or an object with velocities(t) -> ((bx, by), (tx, ty)), the in-plane velocities of the bottom and
+        the top wall at time t (the library's built-in rule, uammd_hip.h).  If it has updateSimulationTime(t) it hears the four times of
+        a step like any updatable; velocities(t) is asked at the three sub-step times, each before the ghost fills of that sub-stage, and
+        at t = 0 on construction."""
 
         def __init__(self, shearViscosity=-1.0, bulkViscosity=-1.0, speedOfSound=-1.0, temperature=0.0, dt=-1.0, boxSize=None,
                      cellDim=(-1, -1, -1), hydrodynamicRadius=-1.0, seed=0, initialDensity=None, initialVelocityX=None,
@@ -118,8 +123,8 @@ class ICM_Compressible(Integrator):
 
     def __init__(self, pd, par):
         super().__init__(pd)
-        if par.walls is not None:
-            raise ValueError("[ICM_Compressible] walls are not supported: the solver is triply periodic")
+        if par.walls is not None and not callable(getattr(par.walls, "velocities", None)):
+            raise ValueError("[ICM_Compressible] walls must have velocities(t) -> ((bx, by), (tx, ty))")
         if par.boxSize is None:
             raise ValueError("[ICM_Compressible] Invalid box size")
         L = np.broadcast_to(np.asarray(getattr(par.boxSize, "boxSize", par.boxSize), dtype=np.float64), (3,))
@@ -129,6 +134,7 @@ class ICM_Compressible(Integrator):
             p.cells[k] = int(par.cellDim[k])
         p.shearViscosity, p.bulkViscosity, p.speedOfSound = float(par.shearViscosity), float(par.bulkViscosity), float(par.speedOfSound)
         p.temperature, p.dt, p.hydrodynamicRadius = float(par.temperature), float(par.dt), float(par.hydrodynamicRadius)
+        p.walls = p.WALLS_NONE if par.walls is None else p.WALLS_BUILTIN
         h, cells = C.c_void_p(), (C.c_int * 3)()
         try:
             check(self.lib.uammd_icmc_validate(C.byref(p)))    # checkInputValidity comes first: a refused set draws nothing from the generator
@@ -140,7 +146,14 @@ class ICM_Compressible(Integrator):
             raise
         self.h, self.cells, self.seed = h, [int(c) for c in cells], int(p.seed)
         self.par, self.boxSize, self.updatables, self._noise = par, [float(x) for x in L], [], None
+        self.walls = par.walls
+        if self.walls is not None:                 # the reference's walls object is an updatable (ICM_Compressible.cuh:226)
+            if hasattr(self.walls, "updateSimulationTime"):
+                self.updatables.append(self.walls)
+            self._set_wall_velocities(0.0)
         self._initialize_fluid(par)
+        if self.walls is not None:                 # setUpGhostCells (:418-422)
+            check(self.lib.uammd_icmc_ghost_fill(self.h, current_stream()))
 
     def __del__(self):
         try:
@@ -243,10 +256,38 @@ class ICM_Compressible(Integrator):
                 it.sum(force=True)
             if self.interactors:
                 force = _ptr(pd.getForce("read"))
-        check(self.lib.uammd_icmc_fluid_and_corrector(self.h, pos, force, N, current_stream()))
-        for third in (1.0 / 3.0, 2.0 / 3.0, 1.0):          # callRungeKuttaSubStep, :88-90 (the host calls only order the callbacks)
-            self._update_time((self.steps + third) * dt)
+        thirds = (1.0 / 3.0, 2.0 / 3.0, 1.0)
+        if self.walls is None:
+            check(self.lib.uammd_icmc_fluid_and_corrector(self.h, pos, force, N, current_stream()))
+            for third in thirds:                            # callRungeKuttaSubStep, :88-90 (the host calls only order the callbacks)
+                self._update_time((self.steps + third) * dt)
+        else:                                               # the same step in pieces: each sub-stage's fills see the walls at its time
+            st = current_stream()
+            check(self.lib.uammd_icmc_fluid_begin(self.h, pos, force, N, st))
+            for s, third in enumerate(thirds):              # callRungeKuttaSubStep, :83-93
+                check(self.lib.uammd_icmc_substage(self.h, s, st))
+                t = (self.steps + third) * dt
+                self._update_time(t)
+                self._set_wall_velocities(t)
+                check(self.lib.uammd_icmc_ghost_fill(self.h, st))
+                check(self.lib.uammd_icmc_substage_velocity(self.h, st))
+                check(self.lib.uammd_icmc_ghost_fill(self.h, st))
+            check(self.lib.uammd_icmc_fluid_end(self.h, pos, N, st))
         self.steps += 1
+
+    def _set_wall_velocities(self, t):
+        bottom, top = self.walls.velocities(t)
+        b, u = (C.c_float * 2)(float(bottom[0]), float(bottom[1])), (C.c_float * 2)(float(top[0]), float(top[1]))
+        check(self.lib.uammd_icmc_set_wall_velocities(self.h, C.byref(b), C.byref(u)))
+
+    def getBottomGhostCells(self):
+        """With walls: the bottom ghost plane as (density [ny, nx], velocity [3, ny, nx], momentum [3, ny, nx])."""
+        nx, ny, nz = self.cells
+        rho = torch.empty((ny, nx), dtype=torch.float32, device=self.pd.device)
+        v, g = torch.empty((3, ny, nx), dtype=torch.float32, device=self.pd.device), torch.empty((3, ny, nx), dtype=torch.float32, device=self.pd.device)
+        pv, pg = (C.c_void_p * 3)(*[v[c].data_ptr() for c in range(3)]), (C.c_void_p * 3)(*[g[c].data_ptr() for c in range(3)])
+        check(self.lib.uammd_icmc_get_bottom_ghost(self.h, _ptr(rho), C.byref(pv), C.byref(pg), current_stream()))
+        return rho, v, g
 
 
 class Hydro:
