@@ -272,112 +272,83 @@ UH_D void tile_words(Acc &acc, uint nW, uint candBase, uint tab, uint wbaseV, ui
   TILE_MARK("drain_setup", PBC);
   __builtin_amdgcn_s_setprio(0);  // (see k_lj_tile4: the drain yields to waves that are loading or scanning)
   // ---- drain: every lane walks its own hit words (bit j from the top of word w = slot 2 j + h of the word) ----
-  // cw / cb = the word being consumed and the LDS address of its slot h, nw / nb = the next one; word nW of every lane is zero and a
-  // lane never moves past word nW - 1 (the look-ahead reads word nW: a row of the table that exists, never consumed).  A lane
-  // without a set bit in cw takes a dead slot: ffbh(0) = -1 addresses slot -2 of the word — staged data of another row or the two
+  // cw / cb = the word being consumed and the LDS address of its slot h; nw / nb = the next word, tw / tb = the one after it.  Word nW
+  // of every lane is zero and a lane never moves past word nW - 1 (the look-ahead reads rows <= nW: rows of the table that exist).  A
+  // lane without a set bit in cw takes a dead slot: ffbh(0) = -1 addresses slot -2 of the word — staged data of another row or the two
   // guard slots in front of the buffer, finite either way — with weight 0.
   *(LdsU *)(uintptr_t)(myMask + 256u * nW) = 0u;
   const uint wabsTab = tab + 4u * (uint)((kMaxW + 1) * 64 + (kMaxW + 2) * hi);  // candBase + 16 hi + wbase[w]
+  // row nW of either table (opaque: otherwise the compiler adds nW to the row index in every iteration, one more instruction)
+  uint maskEnd = myMask + 256u * nW, wabsEnd = wabsTab + 4u * nW;
+  asm("" : "+v"(maskEnd), "+v"(wabsEnd));
   uint cw = *(const LdsU *)(uintptr_t)myMask;
-  uint nw = *(const LdsU *)(uintptr_t)(myMask + 256u);
   uint cb = *(const LdsU *)(uintptr_t)wabsTab;
-  uint nb = *(const LdsU *)(uintptr_t)(wabsTab + 4u);
-  uint wi1 = 1;  // 1 + index of cw, <= nW
-  unsigned long long more;  // lanes with wi1 < nW
-  asm("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(more) : "v"(wi1), "s"(nW));
-  // Two pairs per iteration (instruction-level parallelism for the rcp / polynomial chains, two LDS reads in flight): advance to the
-  // next word when this one is used up, then take the TWO highest set bits; a word with an odd number of hits leaves one dead slot:
-  // 19 iterations per tile against 35 with one pair per iteration on a model liquid.
-  auto pop2 = [&](bool &live0, bool &live1, uint &a0, uint &a1) {
-    // advance: cw == 0 and words left.  (Lane masks by hand: from `wi1 += adv` the compiler makes a select and an add, from a ballot
-    // of adv a select and a compare; the mask of the compare is the carry-in of one v_addc.)  The look-ahead holds ONE word: a lane that
-    // advances takes it, and the word after its new index is requested at once (a lane that stays re-reads the same one) — the request
-    // has the whole iteration to arrive.  (Round 6; until then the word after the next was requested at the top of the iteration and
-    // selected a few instructions later, two more selects per iteration: 0.1344 -> 0.1328 ms per launch, tools/time_lj.py with REPS=2000,
-    // four interleaved runs each, +- 0.0002.)
+  uint nw, nb, tw, tb;
+  // u = (1 + index of cw) - nW, in [1 - nW, 0]: words are left while u < 0.  Counting toward zero makes the end of a lane's words the
+  // CARRY of the advance's own add (u: -1 -> 0), so `more` is kept with scalar instructions: no compare per advance.
+  uint u = 1u - nW;
+  unsigned long long more;  // lanes with words left
+  asm("v_cmp_gt_i32_e64 %0, 0, %1" : "=s"(more) : "v"(u));
+  // the look-ahead: rows 1 + index of cw and the one behind it.  (A lane on its last word, u = 0, reads rows nW - 1 and nW instead of
+  // nW and nW + 1: it never takes either, and row kMaxW + 1 does not exist.)
+  auto look = [&]() {
+    const int uc = min((int)u, -1);
+    const uint am = maskEnd + 256u * (uint)uc, ab = wabsEnd + 4u * (uint)uc;
+    nw = *(const LdsU *)(uintptr_t)am;
+    tw = *(const LdsU *)(uintptr_t)(am + 256u);
+    nb = *(const LdsU *)(uintptr_t)ab;
+    tb = *(const LdsU *)(uintptr_t)(ab + 4u);
+  };
+  // advance: cw == 0 and words left.  (Lane masks by hand: from `u += adv` the compiler makes a select and an add, from a ballot of adv
+  // a select and a compare; the mask of the compare is the carry-in of one v_addc, whose carry-out ends `more`.)
+  auto advance = [&](bool shift) {
     unsigned long long adv, co;
     asm("v_cmp_eq_u32_e64 %0, 0, %1" : "=s"(adv) : "v"(cw));
-    adv &= more;
+    // (the two mask operations by hand as well: written `adv &= more` and `more &= ~co`, the several-types instantiations compute them
+    // with vector instructions and hand the selects a mask in vector registers, which does not assemble)
+    asm("s_and_b64 %0, %1, %2" : "=s"(adv) : "s"(adv), "s"(more) : "scc");
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cw) : "v"(cw), "v"(nw), "s"(adv));
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cb) : "v"(cb), "v"(nb), "s"(adv));
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(wi1), "=s"(co) : "v"(wi1), "s"(adv));
-    nw = *(const LdsU *)(uintptr_t)(myMask + 256u * wi1);
-    nb = *(const LdsU *)(uintptr_t)(wabsTab + 4u * wi1);
-    asm("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(more) : "v"(wi1), "s"(nW));
-    live0 = cw != 0;
-    const uint k0 = (uint)__builtin_clz_or_neg1(cw);
-    cw &= ~(0x80000000u >> (k0 & 31u));
-    live1 = cw != 0;
-    const uint k1 = (uint)__builtin_clz_or_neg1(cw);
-    cw &= ~(0x80000000u >> (k1 & 31u));
-    a0 = cb + (k0 << 5);
-    a1 = cb + (k1 << 5);
-  };
-#ifdef UAMMD_TILE_POP3
-  // VARIANT (tools/variants_tile.sh pop3; measured and not kept): THREE pairs per iteration — fewer loop and word-advance
-  // instructions per pair, more dead slots (a word's hit count is rarely a multiple of three).
-  auto pop3 = [&](bool &live0, bool &live1, bool &live2, uint &a0, uint &a1, uint &a2) {
-    const uint tw = *(const LdsU *)(uintptr_t)(myMask + 256u * wi1 + 256u);
-    const uint tb = *(const LdsU *)(uintptr_t)(wabsTab + 4u * wi1 + 4u);
-    unsigned long long adv, co;
-    asm("v_cmp_eq_u32_e64 %0, 0, %1" : "=s"(adv) : "v"(cw));
-    adv &= more;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cw) : "v"(cw), "v"(nw), "s"(adv));
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cb) : "v"(cb), "v"(nb), "s"(adv));
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(nw) : "v"(nw), "v"(tw), "s"(adv));
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(nb) : "v"(nb), "v"(tb), "s"(adv));
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(wi1), "=s"(co) : "v"(wi1), "s"(adv));
-    asm("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(more) : "v"(wi1), "s"(nW));
-    live0 = cw != 0;
-    const uint k0 = (uint)__builtin_clz_or_neg1(cw);
-    cw &= ~(0x80000000u >> (k0 & 31u));
-    live1 = cw != 0;
-    const uint k1 = (uint)__builtin_clz_or_neg1(cw);
-    cw &= ~(0x80000000u >> (k1 & 31u));
-    live2 = cw != 0;
-    const uint k2 = (uint)__builtin_clz_or_neg1(cw);
-    cw &= ~(0x80000000u >> (k2 & 31u));
-    a0 = cb + (k0 << 5);
-    a1 = cb + (k1 << 5);
-    a2 = cb + (k2 << 5);
-  };
-  bool lN0, lN1, lN2;
-  uint a0, a1, a2;
-  pop3(lN0, lN1, lN2, a0, a1, a2);
-  f4t cN0 = *(const LdsF4 *)(uintptr_t)a0, cN1 = *(const LdsF4 *)(uintptr_t)a1, cN2 = *(const LdsF4 *)(uintptr_t)a2;
-  while (__any(lN0) || more != 0) {
-    TILE_MARK("drain_body", PBC);
-    const f4t c0 = cN0, c1 = cN1, c2 = cN2;
-    const bool l0 = lN0, l1 = lN1, l2 = lN2;
-    pop3(lN0, lN1, lN2, a0, a1, a2);
-    cN0 = *(const LdsF4 *)(uintptr_t)a0;
-    cN1 = *(const LdsF4 *)(uintptr_t)a1;
-    cN2 = *(const LdsF4 *)(uintptr_t)a2;
-    real3f r0, r1, r2;
-    float f0, f1, f2, e0, e1, e2;
-    if (NT != 0) {
-      tile_eval<PBC, WE, NT == 2>(box, p1, pi, c0, r0, f0, e0);
-      tile_eval<PBC, WE, NT == 2>(box, p1, pi, c1, r1, f1, e1);
-      tile_eval<PBC, WE, NT == 2>(box, p1, pi, c2, r2, f2, e2);
-    } else {
-      tile_eval<PBC, WE>(box, lj_lookup(tbl, ntypes, (int)pi.w, (int)c0.w), pi, c0, r0, f0, e0);
-      tile_eval<PBC, WE>(box, lj_lookup(tbl, ntypes, (int)pi.w, (int)c1.w), pi, c1, r1, f1, e1);
-      tile_eval<PBC, WE>(box, lj_lookup(tbl, ntypes, (int)pi.w, (int)c2.w), pi, c2, r2, f2, e2);
+    if (shift) {
+      asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(nw) : "v"(nw), "v"(tw), "s"(adv));
+      asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(nb) : "v"(nb), "v"(tb), "s"(adv));
     }
-    lj_acc<WE, WV>(acc, r0, l0 ? f0 : 0.0f, l0 ? e0 : 0.0f);
-    lj_acc<WE, WV>(acc, r1, l1 ? f1 : 0.0f, l1 ? e1 : 0.0f);
-    lj_acc<WE, WV>(acc, r2, l2 ? f2 : 0.0f, l2 ? e2 : 0.0f);
-  }
-#else
+    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(u), "=s"(co) : "v"(u), "s"(adv));
+    asm("s_andn2_b64 %0, %1, %2" : "=s"(more) : "s"(more), "s"(co) : "scc");
+  };
+  // Two pairs per iteration (instruction-level parallelism for the rcp / polynomial chains, two LDS reads in flight), and a word advance
+  // in front of EITHER pair: a lane whose word is used up by the first pair takes the second from the next word in the same iteration,
+  // so a word with an odd number of hits no longer leaves a dead slot and an empty word costs a pair slot, not an iteration (tools/
+  // drain_model.py: 0.86 of the iterations of one advance per iteration on a model liquid).  Every lane still takes exactly its own
+  // bits, from the top of a word and word after word: the sums are the same bits.  The look-ahead holds TWO words: the first advance
+  // shifts it, the second takes what is left, and both are requested again behind the second advance — the request has the whole
+  // iteration to arrive.  (One word, requested again after each advance, makes every iteration wait for LDS between its two pairs.)
+  auto pop2 = [&](bool &live0, bool &live1, uint &a0, uint &a1) {
+    advance(true);
+    live0 = cw != 0;
+    const uint k0 = (uint)__builtin_clz_or_neg1(cw);
+    cw &= ~(0x80000000u >> (k0 & 31u));
+    a0 = cb + (k0 << 5);
+    advance(false);
+    look();
+    live1 = cw != 0;
+    const uint k1 = (uint)__builtin_clz_or_neg1(cw);
+    cw &= ~(0x80000000u >> (k1 & 31u));
+    a1 = cb + (k1 << 5);
+  };
   bool lN0, lN1;
   uint a0, a1;
+  look();
   pop2(lN0, lN1, a0, a1);
   f4t cN0 = *(const LdsF4 *)(uintptr_t)a0, cN1 = *(const LdsF4 *)(uintptr_t)a1;
   // some lane still holds a pair or has words left (empty trailing words are walked through).  (The condition as ONE scalar word and a
   // for loop: written `while (__any(lN0) || more != 0)` the compiler split the loop into two blocks around the test and carried the three
   // force sums through register copies — four v_mov per iteration and non-destructive v_fma; this form is a single block with v_fmac
-  // accumulators: 61 -> 57 vector instructions per iteration, 0.1328 -> 0.1314 ms per launch, tools/time_lj.py with REPS=2000.)
-  for (unsigned long long busy = __builtin_amdgcn_ballot_w64(lN0) | more; busy != 0; busy = __builtin_amdgcn_ballot_w64(lN0) | more) {
+  // accumulators.)  BOTH slots are in the test: a lane that walks through an empty word in front of its first pair and into its last
+  // word in front of the second holds a pair in the second slot alone, with no words left.
+  // (two ballots: the lane masks exist already, their OR is scalar; from `lN0 | lN1` the compiler ORs the two words and compares again)
+  auto busyLanes = [&]() { return __builtin_amdgcn_ballot_w64(lN0) | __builtin_amdgcn_ballot_w64(lN1) | more; };
+  for (unsigned long long busy = busyLanes(); busy != 0; busy = busyLanes()) {
     TILE_MARK("drain_body", PBC);
     const f4t c0 = cN0, c1 = cN1;
     const bool l0 = lN0, l1 = lN1;
@@ -396,7 +367,6 @@ UH_D void tile_words(Acc &acc, uint nW, uint candBase, uint tab, uint wbaseV, ui
     lj_acc<WE, WV>(acc, r0, l0 ? f0 : 0.0f, l0 ? e0 : 0.0f);
     lj_acc<WE, WV>(acc, r1, l1 ? f1 : 0.0f, l1 ? e1 : 0.0f);
   }
-#endif
   TILE_MARK("drain_end", PBC);
 }
 
