@@ -565,6 +565,42 @@ int uammd_fcm_set_option(uammd_fcm *h, const char *name, int value);
 #define UAMMD_FCM_UPDATE_BIN 2           /* k_fcm_update_bin that also bins the positions it writes */
 #define UAMMD_FCM_UPDATE_PLAIN 3         /* k_fcm_update_bin without binning */
 int uammd_fcm_last_preparation(uammd_fcm *h, int out[2]);
+/* test hook: the two ends of a solve on their own, through the solve's own launch code.  Grids are the solver's three planar real
+ * grids, [3][nz][ny][2 * (nx / 2 + 1)] floats.  To the handle's bookkeeping either stage is a completed solve (the noise counter stays).
+ *   UAMMD_FCM_PROBE_SPREAD  prepares the stencils as a solve of (d_pos, d_force) would — UAMMD_FCM_PROBE_POSITIONS_KEPT as the flag of
+ *                           uammd_fcm_step_euler_maruyama —, runs the spread the handle would launch, stops in front of the forward FFT
+ *                           and copies the grids to d_grid.  UAMMD_FCM_PROBE_NAN_FILL: the grids hold quiet NaNs before a tile-owned
+ *                           spread, which has no memset and must write every node (the atomic spread keeps its memset).
+ *   UAMMD_FCM_PROBE_GATHER  prepares the stencils of d_pos without forces and runs the gather that the handle's options select on the
+ *                           caller's d_grid (interleaved by k_fcm_interleave where the gather reads a float4 grid) into
+ *                           d_linearVelocity real3[N].  UAMMD_FCM_PROBE_PACKED: the caller supplies d_inter instead, [nz][ny][nx] nodes
+ *                           of three floats as UAMMD_FCM_FFT_TARGET_PACKED writes them, and the packed k_fcm_gather_inter reads it (in
+ *                           a solve: grids above 128 MB).  UAMMD_FCM_PROBE_ACCUMULATE: the output is added to, this call only.
+ * info[UAMMD_FCM_PROBE_INFO_LEN] (may be null) says what ran:
+ *   spread  [0] stage, [1] UAMMD_FCM_PREP_*, [2] 1 tile-owned / 0 atomic, [3] waves per tile W, [4] slot layout, [5] compile-time edge E,
+ *           [6] speculative first round, [7..9] tile edge per axis, [10] list entries per chunk, [11] slot capacity, [12] lanes per
+ *           particle and [13] UAMMD_FCM_PREP_KERNEL_* of the preparation kernel this call launched, noted at its launch
+ *   gather  [0] stage, [1] UAMMD_FCM_PREP_*, [2] UAMMD_FCM_GATHER_*, [3] R (inter) or S (half), [4] particles per wave P, [5] SZMAX,
+ *           [6] packed, [7] accumulate, [12], [13] as above */
+#define UAMMD_FCM_PROBE_SPREAD 1
+#define UAMMD_FCM_PROBE_GATHER 2
+#define UAMMD_FCM_PROBE_POSITIONS_KEPT 1
+#define UAMMD_FCM_PROBE_NAN_FILL 2
+#define UAMMD_FCM_PROBE_PACKED 4
+#define UAMMD_FCM_PROBE_ACCUMULATE 8
+/* (not a flag) the length of info */
+#define UAMMD_FCM_PROBE_INFO_LEN 16
+#define UAMMD_FCM_PREP_KERNEL_NONE 0      /* the atomic spread, or a slot layout claimed from the previous step */
+#define UAMMD_FCM_PREP_KERNEL_PREPARE 1   /* k_fcm_prepare */
+#define UAMMD_FCM_PREP_KERNEL_STEP_PREP 2 /* k_fcm_step_prep without the update */
+#define UAMMD_FCM_GATHER_ATOMIC 0 /* k_fcm_ibm */
+#define UAMMD_FCM_GATHER_TILE 1   /* k_fcm_gather_tile */
+#define UAMMD_FCM_GATHER_PREP 2   /* k_fcm_gather_prep */
+#define UAMMD_FCM_GATHER_INTER 3  /* k_fcm_gather_inter<R, P, packed> */
+#define UAMMD_FCM_GATHER_COL 4    /* k_fcm_gather_col<P, SZMAX> */
+#define UAMMD_FCM_GATHER_HALF 5   /* k_fcm_gather_half<S, SZMAX> */
+int uammd_fcm_probe(uammd_fcm *h, int stage, const float *d_pos, const float *d_force, int numberParticles, int flags, float *d_grid,
+                    float *d_inter, float *d_linearVelocity, int *info, void *stream);
 
 /* Torques and rotation (FCM_impl.cuh:306-358, :590-649; FCM_kernels.cuh:60-80; BDHI_FCM.cu:67-92).  The torque window is
  * GaussianTorque(width = a/(6 sqrt(pi))^(1/3), h, tolerance); torques are spread with it, half their curl is added to the

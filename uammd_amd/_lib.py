@@ -374,6 +374,7 @@ SIGNATURES = {
     "uammd_fcm_set_seed2": (_i, [_vp, _u]),
     "uammd_fcm_set_option": (_i, [_vp, C.c_char_p, _i]),
     "uammd_fcm_last_preparation": (_i, [_vp, C.POINTER(_i)]),
+    "uammd_fcm_probe": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.POINTER(_i), _vp]),
     "uammd_fcm_torque_gaussian_kernel": (_i, [_f, _f, _f, C.POINTER(IBMKernel)]),
     "uammd_fcm_set_torque_kernel": (_i, [_vp, C.POINTER(IBMKernel)]),
     "uammd_fcm_displacements_torque": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp]),

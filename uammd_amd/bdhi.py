@@ -288,6 +288,43 @@ class FCM_impl:
         check(self.lib.uammd_fcm_last_preparation(self.h, out))
         return int(out[0]), int(out[1])
 
+    # uammd_fcm_probe (include/uammd_hip.h, UAMMD_FCM_PROBE_* and UAMMD_FCM_GATHER_*)
+    PROBE_SPREAD, PROBE_GATHER = 1, 2
+    GATHER_FORMS = ("atomic", "tile", "prep", "inter", "col", "half")
+    PREP_KERNELS = (None, "k_fcm_prepare", "k_fcm_step_prep")
+
+    def probe(self, stage, pos, force=None, numberParticles=None, grid=None, inter=None, out=None, positions_kept=False, nan_fill=False,
+              accumulate=False):
+        """Test hook: one end of a solve through the solve's own launch code.  PROBE_SPREAD returns (grids, info): the three planar real
+        grids (3, nz, ny, 2 * (nx // 2 + 1)) in front of the forward FFT.  PROBE_GATHER returns (velocities (N, 3), info), gathered from
+        `grid` in that layout or, packed, from `inter` (nz, ny, nx, 3); `out` with accumulate=True is added to.  info names what ran."""
+        n = int(pos.shape[0] if numberParticles is None else numberParticles)
+        nx, ny, nz = self.cells
+        shape = (3, nz, ny, 2 * (nx // 2 + 1))
+        raw = (C.c_int * 16)()
+        if stage == self.PROBE_SPREAD:
+            grid = torch.empty(shape, dtype=torch.float32, device=pos.device)
+            check(self.lib.uammd_fcm_probe(self.h, 1, _ptr(pos), _ptr(force), n, (1 if positions_kept else 0) | (2 if nan_fill else 0),
+                                           _ptr(grid), None, None, raw, current_stream()))
+            r = [int(v) for v in raw]
+            return grid, {"preparation": r[1], "tiles": bool(r[2]), "W": r[3], "slots": bool(r[4]), "E": r[5], "spec": bool(r[6]),
+                          "tile": tuple(r[7:10]), "capEntries": r[10], "slotCap": r[11], "lanes": r[12], "prepKernel": self.PREP_KERNELS[r[13]]}
+        if stage != self.PROBE_GATHER:
+            raise ValueError(f"probe: stage = {stage}")
+        src, want = (inter, (nz, ny, nx, 3)) if inter is not None else (grid, shape)
+        if src is None or src.dtype != torch.float32 or not src.is_contiguous() or tuple(src.shape) != want:
+            raise ValueError(f"probe: the grid must be contiguous float32 of shape {want}")
+        if out is None:
+            if accumulate:
+                raise ValueError("probe: accumulate needs out")
+            out = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
+        check(self.lib.uammd_fcm_probe(self.h, 2, _ptr(pos), None, n, (4 if inter is not None else 0) | (8 if accumulate else 0),
+                                       _ptr(grid) if inter is None else None, _ptr(inter) if inter is not None else None, _ptr(out), raw,
+                                       current_stream()))
+        r = [int(v) for v in raw]
+        return out, {"preparation": r[1], "form": self.GATHER_FORMS[r[2]], "R": r[3], "P": r[4], "SZMAX": r[5], "packed": bool(r[6]),
+                     "accumulate": bool(r[7]), "lanes": r[12], "prepKernel": self.PREP_KERNELS[r[13]]}
+
     def seed2(self, value=None):
         if value is None:
             v = C.c_uint(0)

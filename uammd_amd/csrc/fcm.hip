@@ -22,6 +22,7 @@
 #include "rocfft_plans.hpp"
 #include "saru.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <type_traits>
@@ -70,6 +71,7 @@ struct FCM {
   DeviceBuffer gridBuf, gridBufT, interBuf, prepOrigin, prepWeights, prepTileOf, prepRank, prepTileCount, prepTileStart, prepSorted;
   int emVelN = 0;
   DeviceBuffer emVel;              // velocities of uammd_fcm_step_euler_maruyama when the caller keeps none
+  int ranPrepKernel = 0, ranPrepLanes = 0;   // the preparation kernel that the last fcm_prepare launched, noted at the launch (uammd_fcm_probe: UAMMD_FCM_PREP_KERNEL_*)
   FcmPrepState prep;              // which preparation each solve takes, and what the counters and the entry order hold (fcm_prep_state.hpp)
   bool useTiles = false;   // grid divisible by the tile and >= 3 tiles per dimension
   int3 ntiles{0, 0, 0};
@@ -555,7 +557,7 @@ k_fcm_spread_tile(float *__restrict__ g0, int3 n, int nxpad, size_t plane, size_
     if (ux < 0) ux += ntiles.x;
     if (uy < 0) uy += ntiles.y;
     if (uz < 0) uz += ntiles.z;
-    specShift = (td.x * dx + 16) | (td.y * dy + 16) << 7 | (td.z * dz + 16) << 14;
+    specShift = (td.x * dx + 16) + ((td.y * dy + 16) << 7) + ((td.z * dz + 16) << 14);   // (added as myShift below, though steps 0 / -1 keep every field >= 7)
     if (j < pr.cap) specRec = pr.rec[(size_t)(ux + ntiles.x * (uy + ntiles.y * uz)) * pr.cap + j];
   }
   if (threadIdx.x < kRanges) {
@@ -571,8 +573,11 @@ k_fcm_spread_tile(float *__restrict__ g0, int3 n, int nxpad, size_t plane, size_
     if (nb < 27) myTile = ux + ntiles.x * (uy + ntiles.y * uz);
     // a record's origin is relative to its own tile (in [0, edge), biased by 8): in this tile's frame that is + one tile edge per tile
     // step (steps 0, -1, -2); with + 16 more every field of the shift is >= 0 and every field of record + shift is (origin in this
-    // tile's frame) + 24, in [8, 31]: no carry or borrow between the 7-bit fields
-    myShift = (td.x * dx + 16) | (td.y * dy + 16) << 7 | (td.z * dz + 16) << 14;
+    // tile's frame) + 24, in [8, 31]: no carry or borrow between the 7-bit fields.  That holds for edges up to 8; with a 9-node edge a
+    // field of the shift at step -2 is -2 (supports 11 .. 16), so the fields are ADDED, not or-ed: the sum is then the number whose
+    // base-128 digits are the fields' sums, each in [6, 32], whatever the sign of a part (or-ed, the -2 set every higher bit and the
+    // step -2 sources of such a grid landed on wrong nodes: tests/test_gpu_fcm_stages.py, 27^3 at support 16)
+    myShift = (td.x * dx + 16) + ((td.y * dy + 16) << 7) + ((td.z * dz + 16) << 14);
     int s, e;
     if (SLOTS) {
       const int c = pr.slotCount[myTile];
@@ -803,7 +808,7 @@ k_fcm_spread_tile(float *__restrict__ g0, int3 n, int nxpad, size_t plane, size_
           ddy -= ddy > 0 ? ntiles.y : 0;
           ddz -= ddz > 0 ? ntiles.z : 0;
           if (ddx < -2 || ddy < -2 || ddz < -2) { live[u] = false; ddx = ddy = ddz = 0; }
-          org[u] = (td.x * ddx + 16) | (td.y * ddy + 16) << 7 | (td.z * ddz + 16) << 14;
+          org[u] = (td.x * ddx + 16) + ((td.y * ddy + 16) << 7) + ((td.z * ddz + 16) << 14);   // (added: see myShift)
         }
         org[u] += (int)(rec[u] >> 42);
         key[u] = (int)(rec[u] & 0x1fffffull);
@@ -1261,41 +1266,46 @@ __global__ void __launch_bounds__(64 * kGatherWaves) k_fcm_gather_half(float *__
 // float4 grid with every load of a thread in flight together, 72 us against 47 us for the kernel above: three workgroups per CU do not
 // hide the window's round trip and the per-particle shuffle chains.  Not kept.)
 static void launch_gather_inter(hipStream_t st, float *vout, const float4 *gi, int N, int3 n, int3 support, float dV, FastDiv dsx,
-                                FastDiv dsxy, const FcmPrep &pr, bool accumulate, int perWave = 2, bool packed = false) {
+                                FastDiv dsxy, const FcmPrep &pr, bool accumulate, int perWave = 2, bool packed = false, int *ran = nullptr) {
+  // ran (uammd_fcm_probe): {UAMMD_FCM_GATHER_*, R or S, P, SZMAX} of the instantiation launched below
+  const auto note = [ran](int form, int rs, int P, int szmax) { if (ran) { ran[0] = form; ran[1] = rs; ran[2] = P; ran[3] = szmax; } };
   // the column form where the float4 grid stays in the 256 MB Infinity Cache (C4: 39.5 -> 32.9 us; at C5, a 268 MB grid read from HBM,
   // its six partly filled loads per particle lose to the four full ones: 126 against 112 us)
   const size_t nodes = (size_t)n.x * n.y * n.z;
   static const int halfMode = getenv("UAMMD_FCM_GATHER_HALF") ? atoi(getenv("UAMMD_FCM_GATHER_HALF")) : 1;   // (A/B runs: 0 off, 2 also on grids read from HBM)
   if (packed) {  // (fcm_inter_packed: a grid read from HBM, 12 bytes per node; the float4 forms below do not apply)
     const int rounds = (support.x * support.y * support.z + 63) / 64;
-    const int P = rounds <= 4 ? (perWave >= 4 ? 4 : 2) : 1;
+    // (P as instantiated below: up to two rounds always two particles per wave.  It used to be 4 with option "gather_per_wave" = 4 there
+    // as well, and a grid sized for four per wave under a kernel that takes two left half of the particles ungathered — supports 3, 4, 5
+    // on a packed grid: tests/test_gpu_fcm_stages.py, test_gather_forms[packed-1-2-per-wave-4] and [packed-2-2-per-wave-4])
+    const int P = rounds <= 2 ? 2 : rounds <= 4 ? (perWave >= 4 ? 4 : 2) : 1;
     const dim3 g((N + kGatherWaves * P - 1) / (kGatherWaves * P)), b(64 * kGatherWaves);
-#define UH_GIP(RR, PP) hipLaunchKernelGGL((k_fcm_gather_inter<RR, PP, true>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate)
+#define UH_GIP(RR, PP) do { note(UAMMD_FCM_GATHER_INTER, RR, PP, 0); hipLaunchKernelGGL((k_fcm_gather_inter<RR, PP, true>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate); } while (0)
     if (rounds <= 1) UH_GIP(1, 2); else if (rounds <= 2) UH_GIP(2, 2); else if (rounds <= 4) { if (P == 4) UH_GIP(4, 4); else UH_GIP(4, 2); } else UH_GIP(8, 1);
 #undef UH_GIP
     return;
   }
   if (halfMode == 2 && perWave >= 0 && support.x == 6 && support.y == 6 && support.z <= 8 && nodes * sizeof(float4) < ((size_t)1 << 32)) {
     const dim3 g((N + kGatherWaves * 2 - 1) / (kGatherWaves * 2)), b(64 * kGatherWaves);
-    if (support.z <= 6) hipLaunchKernelGGL((k_fcm_gather_half<6, 6>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
-    else hipLaunchKernelGGL((k_fcm_gather_half<6, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
+    if (support.z <= 6) { note(UAMMD_FCM_GATHER_HALF, 6, 2, 6); hipLaunchKernelGGL((k_fcm_gather_half<6, 6>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
+    else { note(UAMMD_FCM_GATHER_HALF, 6, 2, 8); hipLaunchKernelGGL((k_fcm_gather_half<6, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
     return;
   }
   if (perWave >= 0 && support.x <= 8 && support.y <= 8 && support.z <= 8 && nodes * sizeof(float4) <= ((size_t)128 << 20)) {
     constexpr int P = 2;  // (32.9 / 33.5 / 36.4 us with 2 / 3 / 4 particles per wave at C4)
     const dim3 g((N + kGatherWaves * P - 1) / (kGatherWaves * P)), b(64 * kGatherWaves);
     if (support.x == 6 && support.y == 6 && halfMode != 0) {
-      if (support.z <= 6) hipLaunchKernelGGL((k_fcm_gather_half<6, 6>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
-      else hipLaunchKernelGGL((k_fcm_gather_half<6, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
+      if (support.z <= 6) { note(UAMMD_FCM_GATHER_HALF, 6, 2, 6); hipLaunchKernelGGL((k_fcm_gather_half<6, 6>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
+      else { note(UAMMD_FCM_GATHER_HALF, 6, 2, 8); hipLaunchKernelGGL((k_fcm_gather_half<6, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
       return;
     }
     if (support.x == 7 && support.y == 7 && halfMode != 0) {
-      if (support.z <= 7) hipLaunchKernelGGL((k_fcm_gather_half<7, 7>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
-      else hipLaunchKernelGGL((k_fcm_gather_half<7, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
+      if (support.z <= 7) { note(UAMMD_FCM_GATHER_HALF, 7, 2, 7); hipLaunchKernelGGL((k_fcm_gather_half<7, 7>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
+      else { note(UAMMD_FCM_GATHER_HALF, 7, 2, 8); hipLaunchKernelGGL((k_fcm_gather_half<7, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
       return;
     }
-    if (support.z <= 6) hipLaunchKernelGGL((k_fcm_gather_col<2, 6>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate);
-    else hipLaunchKernelGGL((k_fcm_gather_col<2, 8>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate);
+    if (support.z <= 6) { note(UAMMD_FCM_GATHER_COL, 0, 2, 6); hipLaunchKernelGGL((k_fcm_gather_col<2, 6>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate); }
+    else { note(UAMMD_FCM_GATHER_COL, 0, 2, 8); hipLaunchKernelGGL((k_fcm_gather_col<2, 8>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate); }
     return;
   }
   if (perWave < 0) perWave = -perWave;  // (test hook: a negative value asks for k_fcm_gather_inter with that many particles per wave)
@@ -1303,7 +1313,7 @@ static void launch_gather_inter(hipStream_t st, float *vout, const float4 *gi, i
   // (measured at C4, support 6: 47.3 / 40.2 / 40.8 us with 1 / 2 / 4 particles per wave)
   const int P = (rounds <= 4 && perWave >= 2) ? (perWave >= 4 ? 4 : 2) : 1;
   const dim3 g((N + kGatherWaves * P - 1) / (kGatherWaves * P)), b(64 * kGatherWaves);
-#define UH_GI(RR, PP) hipLaunchKernelGGL((k_fcm_gather_inter<RR, PP>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate)
+#define UH_GI(RR, PP) do { note(UAMMD_FCM_GATHER_INTER, RR, PP, 0); hipLaunchKernelGGL((k_fcm_gather_inter<RR, PP>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate); } while (0)
   if (rounds <= 1) { if (P == 4) UH_GI(1, 4); else if (P == 2) UH_GI(1, 2); else UH_GI(1, 1); }
   else if (rounds <= 2) { if (P == 4) UH_GI(2, 4); else if (P == 2) UH_GI(2, 2); else UH_GI(2, 1); }
   else if (rounds <= 4) { if (P == 4) UH_GI(4, 4); else if (P == 2) UH_GI(4, 2); else UH_GI(4, 1); }
@@ -1851,11 +1861,12 @@ static FcmPrep fcm_prep_view(const FCM *f, bool slots, int parity, const float *
 
 // k_fcm_prepare and k_fcm_step_prep are instantiated per window kind and per lanes per particle (at 2e5 particles the chip is full with one
 // lane each): launch(kind, lanes, blocks) gets both as integral constants.  False: the window kind has no such kernel.
+static int fcm_prep_lanes(int N) { return N <= kPrepLanesUpTo ? kPrepLanes : 1; }
 template <class Launch>
 static bool fcm_dispatch_prep(int kind, int N, Launch &&launch) {
 #define UH_KIND(K)                                                                                                               \
   case K:                                                                                                                        \
-    if (N <= kPrepLanesUpTo) launch(std::integral_constant<int, K>{}, std::integral_constant<int, kPrepLanes>{}, dim3((unsigned)(((size_t)N * kPrepLanes + 255) / 256))); \
+    if (fcm_prep_lanes(N) == kPrepLanes) launch(std::integral_constant<int, K>{}, std::integral_constant<int, kPrepLanes>{}, dim3((unsigned)(((size_t)N * kPrepLanes + 255) / 256))); \
     else launch(std::integral_constant<int, K>{}, std::integral_constant<int, 1>{}, dim3((N + 255) / 256));                     \
     return true;
   switch (kind) {
@@ -1903,6 +1914,8 @@ static int fcm_step_prep_run(FCM *f, const FcmStepPrepPlan &p, const FcmPrepInpu
   if (p.zeroSlotCounts) UH_CHECK(hipMemsetAsync(f->prepSlotCount.ptr, 0, sizeof(int) * 2 * ((size_t)nt + 2), st));
   const FcmPrep pr = fcm_prep_view(f, true, p.parity, nullptr);   // (origin: entry -> particle from an earlier solve; rewritten entry by entry)
   if (!fcm_dispatch_prep(f->kern.kind, N, [&](auto kind, auto lanes, dim3 blocks) {
+        f->ranPrepKernel = UAMMD_FCM_PREP_KERNEL_STEP_PREP;
+        f->ranPrepLanes = decltype(lanes)::value;
         hipLaunchKernelGGL((k_fcm_step_prep<decltype(kind)::value, decltype(lanes)::value>), blocks, dim3(256), 0, st, (float4 *)d_pos, v, N, dt, f->grid,
                            f->kern, f->ntiles, pr, N);
       })) return -3;
@@ -1915,6 +1928,8 @@ static int fcm_prepare_run(FCM *f, const float *d_pos, const float *d_force, int
                            bool *slots) {
   const FcmPrepInputs c = fcm_prep_inputs(f, d_pos, d_force, N, st, positionsKept, tiles);
   const FcmSolvePlan p = f->prep.beforeSolve(c);
+  f->ranPrepKernel = UAMMD_FCM_PREP_KERNEL_NONE;
+  f->ranPrepLanes = 0;
   *slots = p.slots();
   *out = FcmPrep{};
   if (p.clearScrambled) f->slotFlagHost[1] = 0;
@@ -1946,6 +1961,8 @@ static int fcm_prepare_run(FCM *f, const float *d_pos, const float *d_force, int
                        f->ntiles, pr, f->kern.support);
   hipLaunchKernelGGL(k_fcm_tile_scan, dim3(1), dim3(1024), 0, st, pr.tileCount, nt, pr.tileStart);
   if (!fcm_dispatch_prep(f->kern.kind, N, [&](auto kind, auto lanes, dim3 blocks) {
+        f->ranPrepKernel = UAMMD_FCM_PREP_KERNEL_PREPARE;
+        f->ranPrepLanes = decltype(lanes)::value;
         hipLaunchKernelGGL((k_fcm_prepare<decltype(kind)::value, decltype(lanes)::value>), blocks, dim3(256), 0, st, (const float4 *)d_pos,
                            (const float4 *)d_force, N, f->grid, f->kern, pr);
       })) return -3;
@@ -2152,15 +2169,26 @@ int uammd_fcm_fft_probe(const int cells[3], int mode, int target, float *d_grid,
   return 0;
 }
 
-// stage: 0 = full pipeline; 1 = stop after spread+FFT+k-space (the Fourier grid can then be exported)
+// what uammd_fcm_probe asks of a solve beyond its stage, and where the launch code below says what it ran
+struct FcmProbe {
+  bool nanFill = false;      // kStageSpread: quiet NaNs in the real grids before a tile-owned spread
+  bool packed = false;       // kStageGather: `inter` is the caller's packed grid; k_fcm_gather_inter<R, P, true> reads it
+  bool accumulate = false;   // kStageGather: the gather adds into the output, this call only
+  const float4 *inter = nullptr;
+  int info[UAMMD_FCM_PROBE_INFO_LEN] = {};
+};
+enum { kStageSolve = 0, kStageFourier = 1, kStageSpread = 2, kStageGather = 3 };
+// stage: 0 = full pipeline; 1 = stop after spread+FFT+k-space (the Fourier grid can then be exported); 2 = stop after the spread (the real
+// grids hold it); 3 = stencils and gather alone, from the real grids as they are (uammd_fcm_probe, which fills them first)
 // half: 0 = the whole solve; 1 = its first half (binning, stencils, spreading, the forward x / y transforms), 2 = the second (z transform,
 // operator and noise, inverse transforms, gather) of a solve whose first half was queued on the same stream with the same arguments —
 // for a caller with other work to queue in between (uammd_pse_far_displacements_half)
 static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float *d_force, int N, float temperature,
-                                  float prefactor, float *d_linearVelocity, int stage, void *stream, bool positionsKept, int half = 0) {
+                                  float prefactor, float *d_linearVelocity, int stage, void *stream, bool positionsKept, int half = 0,
+                                  FcmProbe *probe = nullptr) {
   if (!h) { set_last_error("uammd_fcm_displacements: null argument"); return -1; }
   if (N <= 0) return 0;  // nothing to move (an empty ParticleData has no arrays to point to)
-  if (!d_pos || (!d_linearVelocity && stage == 0)) { set_last_error("uammd_fcm_displacements: null argument"); return -1; }
+  if (!d_pos || (!d_linearVelocity && (stage == kStageSolve || stage == kStageGather))) { set_last_error("uammd_fcm_displacements: null argument"); return -1; }
   FCM *f = reinterpret_cast<FCM *>(h);
   hipStream_t st = (hipStream_t)stream;
   float *g = (float *)f->gridBuf.ptr;
@@ -2194,6 +2222,12 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
       static const bool specDense = getenv("UAMMD_FCM_SPEC_DENSE") != nullptr;
       // (the round lists up to one record per thread at once: the list and its weights must hold a workgroup's worth — capEntries >= 64 W)
       const bool spec = specOn && slots && eight && pr.cap >= 8 * sw && ww / (3 * edge) >= 64 * sw && (sw == 2 || specDense);
+      if (probe) {
+        if (probe->nanFill) UH_CHECK(hipMemsetD32Async((hipDeviceptr_t)g, 0x7fc00000, 3 * f->planeReal, st));   // (the kernel has no memset: it owns every node)
+        const int said[] = {UAMMD_FCM_PROBE_SPREAD, f->prep.lastPreparation(), 1, sw, slots, edge, spec, f->tdim.x, f->tdim.y, f->tdim.z,
+                            std::min(64 * sw, ww / (3 * edge)), pr.cap, f->ranPrepLanes, f->ranPrepKernel};
+        std::copy(said, said + 14, probe->info);
+      }
 #define UH_SPREAD_SPEC(W, E) hipLaunchKernelGGL((k_fcm_spread_tile<W, true, E, true>), sg, sb, lds, st, g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles, pr, ww)
       if (spec) {
         if (sw == 2) { if (edge == kTileMax) UH_SPREAD_SPEC(2, kTileMax); else UH_SPREAD_SPEC(2, kTile); }
@@ -2209,10 +2243,12 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
 #undef UH_SPREAD
 #undef UH_SPREAD_SPEC
     } else {
+      if (probe) probe->info[0] = UAMMD_FCM_PROBE_SPREAD;   // (atomic: no preparation, no tiles — the rest stays 0)
       UH_CHECK(hipMemsetAsync(g, 0, sizeof(float) * 3 * f->planeReal, st));
       hipLaunchKernelGGL((k_fcm_ibm<true>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)d_force,
                          (float *)nullptr, g, N, f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, false);
     }
+    if (stage == kStageSpread) { UH_CHECK(hipGetLastError()); return 0; }
     if (custom) { if (int e = fcm_fft_forward_xy(f, g, st)) return e; }
     else if (int e = f->fft.forward(g)) return e;
   }
@@ -2233,7 +2269,8 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
   const int total = (int)f->planeCplx;
   const KLayout lay{f->grid.cellDim.y, 0, f->planeCplx, (size_t)(f->grid.cellDim.x / 2 + 1) * f->grid.cellDim.y,
                     make_fastdiv(f->grid.cellDim.x / 2 + 1), make_fastdiv(f->grid.cellDim.y)};
-  if (custom) {
+  if (stage == kStageGather) {   // (the real grids are the caller's)
+  } else if (custom) {
     if (int e = fcm_fft_z_operator_y(f, g, d_force != nullptr, noisePrefactor, st)) return e;
   } else {
     hipLaunchKernelGGL(k_fcm_kspace, dim3((total + 255) / 256), dim3(256), 0, st, (float2 *)g, lay,
@@ -2245,34 +2282,80 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
   const bool interPath = tiles && f->interGather && !(tiles && (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6) && f->prep.tileGather);
   if (custom && !interPath) { if (int e = fcm_fft_inverse_x(f, g, nullptr, st)) return e; }
   const bool smallSupport = f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6;
+  const bool accumulate = f->accumulate || (probe && probe->accumulate);
+  int ran[4] = {tiles ? (smallSupport && f->prep.tileGather ? UAMMD_FCM_GATHER_TILE : UAMMD_FCM_GATHER_PREP) : UAMMD_FCM_GATHER_ATOMIC, 0, 0, 0};
   if (tiles && smallSupport && f->prep.tileGather)
     hipLaunchKernelGGL(k_fcm_gather_tile, dim3(f->ntiles.x * f->ntiles.y * f->ntiles.z), bp, 0, st, d_linearVelocity,
                        (const float *)g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles,
-                       f->grid.cellVolume, dsx, dsxy, pr, f->accumulate);
+                       f->grid.cellVolume, dsx, dsxy, pr, accumulate);
   else if (tiles && f->interGather) {
     const size_t nodes = (size_t)f->grid.cellDim.x * f->grid.cellDim.y * f->grid.cellDim.z;
-    if (int e = f->interBuf.reserve(sizeof(float4) * nodes)) return e;
-    const bool packed = custom && fcm_inter_packed(f);
-    if (custom) {  // the inverse x transform writes the interleaved grid itself
+    const bool given = probe && probe->packed;   // (the caller's packed grid instead of the handle's)
+    if (!given)
+      if (int e = f->interBuf.reserve(sizeof(float4) * nodes)) return e;
+    const bool packed = given || (custom && fcm_inter_packed(f));
+    if (given) {
+    } else if (custom) {  // the inverse x transform writes the interleaved grid itself
       if (int e = fcm_fft_inverse_x(f, g, (float4 *)f->interBuf.ptr, st, packed)) return e;
     } else
       hipLaunchKernelGGL(k_fcm_interleave, dim3((unsigned)((nodes + 255) / 256)), bp, 0, st, (const float *)g, f->grid.cellDim, f->nxpad,
                          f->planeReal, zs, (float4 *)f->interBuf.ptr);
-    launch_gather_inter(st, d_linearVelocity, (const float4 *)f->interBuf.ptr, N, f->grid.cellDim, f->kern.support, f->grid.cellVolume,
-                        dsx, dsxy, pr, f->accumulate, f->gatherPerWave, packed);
+    launch_gather_inter(st, d_linearVelocity, given ? probe->inter : (const float4 *)f->interBuf.ptr, N, f->grid.cellDim, f->kern.support,
+                        f->grid.cellVolume, dsx, dsxy, pr, accumulate, f->gatherPerWave, packed, ran);
   } else if (tiles)
     hipLaunchKernelGGL(k_fcm_gather_prep, gp, bp, 0, st, d_linearVelocity, (const float *)g, N, f->grid.cellDim, f->nxpad,
-                       f->planeReal, zs, f->kern.support, f->grid.cellVolume, dsx, dsxy, pr, f->accumulate);
+                       f->planeReal, zs, f->kern.support, f->grid.cellVolume, dsx, dsxy, pr, accumulate);
   else
     hipLaunchKernelGGL((k_fcm_ibm<false>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)nullptr,
-                       d_linearVelocity, g, N, f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, f->accumulate);
+                       d_linearVelocity, g, N, f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, accumulate);
   UH_CHECK(hipGetLastError());
+  if (probe && stage == kStageGather) {
+    const int said[] = {UAMMD_FCM_PROBE_GATHER, f->prep.lastPreparation(), ran[0], ran[1], ran[2], ran[3], ran[0] == UAMMD_FCM_GATHER_INTER && probe->packed,
+                        accumulate, 0, 0, 0, 0, f->ranPrepLanes, f->ranPrepKernel};
+    std::copy(said, said + 14, probe->info);
+  }
   return 0;
 }
 
 int uammd_fcm_displacements_staged(uammd_fcm *h, const float *d_pos, const float *d_force, int N, float temperature,
                                    float prefactor, float *d_linearVelocity, int stage, void *stream) {
   return fcm_displacements_impl(h, d_pos, d_force, N, temperature, prefactor, d_linearVelocity, stage, stream, false);
+}
+
+// The two ends of a solve on their own (include/uammd_hip.h): the stages of fcm_displacements_impl, so what runs is the solve's launch code.
+// To the handle's state a spread probe is a solve with forces and a gather probe a solve without (FcmPrepState::beforeSolve, nothing new).
+int uammd_fcm_probe(uammd_fcm *h, int stage, const float *d_pos, const float *d_force, int N, int flags, float *d_grid, float *d_inter,
+                    float *d_linearVelocity, int *info, void *stream) {
+  if (!h || !d_pos || N <= 0) { set_last_error("uammd_fcm_probe: null argument"); return -1; }
+  FCM *f = reinterpret_cast<FCM *>(h);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t gridBytes = sizeof(float) * 3 * f->planeReal;
+  FcmProbe probe;
+  if (stage == UAMMD_FCM_PROBE_SPREAD) {
+    if (!d_force || !d_grid) { set_last_error("uammd_fcm_probe: the spread needs d_force and d_grid"); return -1; }
+    probe.nanFill = (flags & UAMMD_FCM_PROBE_NAN_FILL) != 0;
+    if (int e = fcm_displacements_impl(h, d_pos, d_force, N, 0.0f, 0.0f, nullptr, kStageSpread, stream, (flags & UAMMD_FCM_PROBE_POSITIONS_KEPT) != 0,
+                                       0, &probe)) return e;
+    UH_CHECK(hipMemcpyAsync(d_grid, f->gridBuf.ptr, gridBytes, hipMemcpyDeviceToDevice, st));
+    if (probe.nanFill) UH_CHECK(hipMemsetAsync(f->gridBuf.ptr, 0, gridBytes, st));   // (the padding columns are nobody's: no NaN stays behind)
+  } else if (stage == UAMMD_FCM_PROBE_GATHER) {
+    probe.packed = (flags & UAMMD_FCM_PROBE_PACKED) != 0;
+    probe.accumulate = (flags & UAMMD_FCM_PROBE_ACCUMULATE) != 0;
+    if (!d_linearVelocity || (probe.packed ? !d_inter : !d_grid)) { set_last_error("uammd_fcm_probe: the gather needs d_linearVelocity and a grid"); return -1; }
+    const bool small = f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6;
+    if (probe.packed && !(f->useTiles && !f->forceAtomicSpread && f->interGather && !(small && f->prep.tileGather))) {
+      set_last_error("uammd_fcm_probe: the handle's options do not select the interleaved gather, which is the one that reads a packed grid");
+      return -2;
+    }
+    probe.inter = (const float4 *)d_inter;
+    if (!probe.packed) UH_CHECK(hipMemcpyAsync(f->gridBuf.ptr, d_grid, gridBytes, hipMemcpyDeviceToDevice, st));
+    if (int e = fcm_displacements_impl(h, d_pos, nullptr, N, 0.0f, 0.0f, d_linearVelocity, kStageGather, stream, false, 0, &probe)) return e;
+  } else {
+    set_last_error("uammd_fcm_probe: stage = %d", stage);
+    return -1;
+  }
+  if (info) std::copy(probe.info, probe.info + UAMMD_FCM_PROBE_INFO_LEN, info);
+  return 0;
 }
 
 // the update of a step: pos += v dt by the kernel that FcmPrepState::afterStepSolve names, which also prepares the next solve
