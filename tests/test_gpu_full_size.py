@@ -172,7 +172,7 @@ def test_fcm_full_size_vs_oracle(hip, o32, n, ncell):
 
 @pytest.mark.parametrize("n,ncell,tol", [(150_000, 216, 1e-3), (120_000, 216, 1e-4)], ids=["216^3-tol1e-3", "216^3-tol1e-4"])
 def test_fcm_grid_beyond_the_infinity_cache_not_a_power_of_two(hip, o32, n, ncell, tol):
-    """Grids whose float4 copy would not stay in the Infinity Cache (> 128 MB) take the gather's 12-byte grid (fcm.hip fcm_inter_packed:
+    """Grids whose float4 copy would not stay in the Infinity Cache (> 128 MB) take the gather's 12-byte grid (fcm_choose_gather, FcmGatherChoice::packed:
     the inverse x pass writes it, k_fcm_gather_inter<R, P, true> reads it in launch order).  C5 is the power-of-two case with support 6;
     here 216 = 2^3 3^3 (the mixed-radix passes) and a second tolerance (a wider support: more rounds of 64 stencil nodes per particle)."""
     from oracle.fcm import FCMOracle

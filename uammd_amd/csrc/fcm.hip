@@ -18,6 +18,7 @@
 //   * all work buffers are owned by the handle; steady state allocates nothing.
 #include "ibm.hpp"
 #include "celllist.hpp"
+#include "fcm_launch_choice.hpp"
 #include "fcm_prep_state.hpp"
 #include "rocfft_plans.hpp"
 #include "saru.hpp"
@@ -32,6 +33,26 @@ namespace uammd_hip {
 
 // PSE far field (FarField.cuh:85-119): hydrodynamic radius, Ewald splitting, kernel splitting, shear strain
 struct PseGreens { float rh, split, eta, shear; bool on; };
+
+// The environment's A/B switches, read once per process at first use: the only getenv of this file.  The choices of
+// fcm_launch_choice.hpp take them as inputs.
+static const FcmSwitches &fcm_switches() {
+  static const FcmSwitches sw = [] {
+    const auto set = [](const char *name) { return getenv(name) != nullptr; };
+    const auto off = [](const char *name) { const char *v = getenv(name); return v && atoi(v) == 0; };   // NAME=0
+    FcmSwitches w;
+    if (const char *v = getenv("UAMMD_FCM_GATHER_HALF")) w.gatherHalf = atoi(v);
+    w.noSpec = set("UAMMD_FCM_NO_SPEC");
+    w.specDense = set("UAMMD_FCM_SPEC_DENSE");
+    w.packedInter = !off("UAMMD_FCM_PACKED_INTER");
+    w.noTile9 = set("UAMMD_FCM_NO_TILE9");
+    w.noPlaneFft = set("UAMMD_FCM_NO_PLANE_FFT");
+    w.slots = !off("UAMMD_FCM_SLOTS");
+    return w;
+  }();
+  return sw;
+}
+static FcmInt3 to_choice(int3 v) { return FcmInt3{v.x, v.y, v.z}; }
 
 // the tile-sorted stencil arrays of a solve (fcm_prepare)
 struct FcmPrep {
@@ -83,13 +104,14 @@ struct FCM {
   bool forceAtomicSpread = false;  // test hook
   bool interGather = true;         // gather from an interleaved float4 copy of the velocity grids (k_fcm_interleave)
   int gatherPerWave = 2;           // particles per wave of k_fcm_gather_inter (1, 2, 4)
-  int spreadWaves = 0;             // waves per tile of k_fcm_spread_tile: 0 = by the tiles' population (spread_waves), 2, 4
+  int spreadWaves = 0;             // waves per tile of k_fcm_spread_tile: 0 = by the tiles' population (fcm_choose_spread), 2, 4
   bool accumulate = false;         // gather adds into the output (IBM::gather semantics; PSE far field)
   int zTileLog2 = 0;               // test / tuning hook: log2 of the fused z pass's node tile (0 = default)
   bool customFFT = true;           // power-of-two grids: the five-pass LDS FFT pipeline of fcm_fft.hpp instead of rocFFT + k_fcm_kspace
   PseGreens pse{0.f, 0.f, 0.f, 0.f, false};  // PSE far field: Hasimoto-split RPY greens function instead of 1/(eta k^2)
   RealFFT fft;             // (the z-slab solver runs its own four plans through this one's info and work buffer)
   unsigned int seed2 = 0;  // the reference's `static uint seed2` (FCM_impl.cuh:517): per-handle here
+  FCM() { prep.slots = fcm_switches().slots; }
   ~FCM() {
     if (slotFlagHost) (void)hipHostFree(slotFlagHost);
   }
@@ -162,8 +184,7 @@ __global__ void __launch_bounds__(256) k_fcm_ibm(const float4 *__restrict__ pos,
 // particle whose stencil overlaps the tile into an LDS copy of the tile (LDS float atomics, conflicts stay
 // inside the CU) and then stores the tile with plain coalesced writes.  Particles are binned by tile with a
 // small counting sort; the per-particle stencil origin and the 3*support 1-D weights are computed ONCE
-// (k_fcm_prepare) and reused by every tile that the particle touches and by the gather.
-constexpr int kTile = 8;
+// (k_fcm_prepare) and reused by every tile that the particle touches and by the gather.  (kTile = 8: fcm_launch_choice.hpp)
 // A particle belongs to the tile of its stencil's ORIGIN (the lowest node, wrapped into the grid): the stencil then reaches from inside
 // that tile towards + only, so a tile's candidates sit in the tiles at offsets -k .. 0 per axis, k = ceil((support - 1) / edge) —
 // eight tiles for the supports and edges of the bench's sizes, where binning by the particle's own cell needed all 27 (660 candidate
@@ -430,52 +451,28 @@ __global__ void __launch_bounds__(256) k_fcm_step_prep(float4 *__restrict__ pos,
 //      (LDS float atomics retire ~1 lane per clock on gfx950: a shared LDS tile kept the LDS pipe 90 % busy and the kernel at
 //      400 us; private LDS copies with read-modify-write were VALU-issue bound at 100 us.)  The four private copies are summed
 //      through LDS when the tile is stored.
-// LDS budget of phase B in words, chosen per call (spread_weight_words): 24 words per listed particle (kSpWT), 6144 = 256 listed
+// LDS budget of phase B in words, chosen per call (fcm_choose_spread, fcm_launch_choice.hpp, with kSpWeightWordsMax): 24 words per listed particle (kSpWT), 6144 = 256 listed
 // particles (a C4 tile lists ~105), 3072 = 128 where tiles are sparse (a C5 tile lists ~26); with the list either fits five
 // workgroups per CU beside the 24.6 KB floor of the final tile sum.
 #ifndef UAMMD_SP_ABLATE   // (timing builds only, tools/variants_fcm.sh: 1 no weights copy, 2 no matrix phase, 4 no tile sum / store, 8 nothing accepted)
 #define UAMMD_SP_ABLATE 0
 #endif
-#ifndef UAMMD_SP_WORDS   // (A/B builds: tools/variants_fcm.sh — 6144 words / 4 candidates per thread: within 1 % of these at C4 and 108^3)
-#define UAMMD_SP_WORDS 6144
-#endif
 #ifndef UAMMD_SP_PER_THREAD
 #define UAMMD_SP_PER_THREAD 2   // (round 5, ~195 candidates per C4 tile since the tiles are the stencil origins': 1 / 2 / 3 -> solve 0.1588 / 0.1595 / 0.1609 ms)
 #endif
-constexpr int kSpWeightWordsMax = UAMMD_SP_WORDS;
 constexpr int kSpWT = 3 * kTile;      // LDS words per listed particle: its weights at the tile's 8 nodes along x, y, z
 // The kernel's layouts are sized by a compile-time tile edge E: 8 (every grid whose axes divide by 4..8) or 9 — round 6, for grids like the
 // PSE far field's 108 = 12 x 9, which otherwise takes 6-node tiles: 5832 tiles listing 137 particles each (799 k particle-tile pairs, 32 %
 // of each matrix product used) against 1728 tiles listing 268 (463 k pairs; 27 of 32 rows and 81 of 96 columns in THREE products per step).
-constexpr int kTileMax = 9;
+// (kTileMax = 9: fcm_launch_choice.hpp)
 constexpr int kSpPerThread = UAMMD_SP_PER_THREAD;       // candidates per thread and round of phase A (768 per round; a C4 tile sees ~660)
 struct SpEntry {
   int o;  // stencil origin in the tile's frame (may be negative), biased by 24 and packed in 7-bit fields: ox | oy << 7 | oz << 14
   int slot;
   float fx, fy, fz;
 };
-// dynamic LDS: float wts[weightWords + 32] | SpEntry list[64 waves + 1]   (a list never holds more entries than the workgroup has threads;
-// +1: phase C reads 8 words per 5-word entry); the waves' private tiles of the final sum alias the same block.  Two-wave tiles with
-// 129 entries instead of 257: 15.6 KB per workgroup, ten of them on a CU — as many as the registers allow — instead of nine.
-static size_t spread_lds_bytes(int weightWords, int waves = 4, int edge = kTile) {
-  const size_t a = sizeof(float) * (size_t)(weightWords + 32) + sizeof(SpEntry) * (64 * waves + 1), b = sizeof(float) * waves * 3 * edge * edge * edge;
-  return a > b ? a : b;
-}
-// two waves per tile where a tile lists few particles (measured at C5, ~26 listed: see DESIGN 5.4), four otherwise
-static int spread_waves(int N, int3 ntiles, int3 support, int3 tdim, int option) {
-  if (option == 2 || option == 4) return option;
-  const double perTile = (double)N / ((double)ntiles.x * ntiles.y * ntiles.z);
-  const double listed = perTile * (1.0 + (support.x - 1) / (double)tdim.x) * (1.0 + (support.y - 1) / (double)tdim.y) * (1.0 + (support.z - 1) / (double)tdim.z);
-  return listed > 48.0 ? 4 : 2;
-}
-static int spread_edge(int3 tdim) { return (tdim.x > kTile || tdim.y > kTile || tdim.z > kTile) ? kTileMax : kTile; }
-static int spread_weight_words(int N, int3 ntiles, int3 support, int3 tdim) {
-  const double perTile = (double)N / ((double)ntiles.x * ntiles.y * ntiles.z);
-  const double listed = perTile * (1.0 + (support.x - 1) / (double)tdim.x) * (1.0 + (support.y - 1) / (double)tdim.y) * (1.0 + (support.z - 1) / (double)tdim.z);
-  const int full = spread_edge(tdim) == kTileMax ? 256 * 3 * kTileMax : kSpWeightWordsMax;   // (256 listed particles either way)
-  return listed > 64.0 ? full : full / 2;
-}
-// W = waves per workgroup: 4, or 2 where the tiles are sparse (spread_waves) — a tile then costs the same chain of round trips for a
+// (dynamic LDS: fcm_spread_lds_bytes of fcm_launch_choice.hpp, given sizeof(SpEntry))
+// W = waves per workgroup: 4, or 2 where the tiles are sparse (fcm_choose_spread) — a tile then costs the same chain of round trips for a
 // few matrix steps: twice the tiles in flight for the same waves.  Measured at C5 (256^3, 6 particles per tile, ~26 listed): 179 / 168 /
 // 224 us with 4 / 2 / 1 waves per tile; at C4 (24 per tile, ~105 listed) 62 / 98 with 4 / 2.
 #ifdef UAMMD_SPREAD_TIMELINE   // diagnostic build (tools/variants_fcm.sh, tools/spread_timeline.py): where a tile's lifetime goes, 100 MHz ticks
@@ -1004,7 +1001,7 @@ __global__ void __launch_bounds__(256) k_fcm_interleave(const float *__restrict_
 // and its four rounds were SIX dependent round trips — 48 us at C4, which is 12 rounds of waves x 6 x ~0.65 us and had been read as
 // an L2 request limit.  Here the record and the weights are requested together, then every node of a chunk of R rounds, then the
 // arithmetic: two round trips per wave.  The sums run in the same order as before (round by round, then the xor reduction).
-constexpr int kGatherWaves = 4;  // (16 waves = 16 consecutive tile-sorted particles per workgroup, to share their lines in the CU's L1: 48.7 against 47.1 us)
+// (kGatherWaves = 4 waves per workgroup: fcm_launch_choice.hpp, which sizes the grids by it)
 // P = particles per wave: the kernel is bound by wave lifetimes (two round trips + the reduction, ~3.8 us, at 32 waves per CU), not by
 // bytes; a wave that carries P particles keeps P R loads in flight for the same two round trips.
 // PK: the grid holds 12 bytes per node (x, y, z) instead of the float4 — for grids too large for the 256 MB Infinity Cache, where the
@@ -1265,60 +1262,131 @@ __global__ void __launch_bounds__(64 * kGatherWaves) k_fcm_gather_half(float *__
 // four waves interpolate the tile's ~24 particles from LDS — was written twice: round 1 on the planar grids, 112 us, and round 3 on the
 // float4 grid with every load of a thread in flight together, 72 us against 47 us for the kernel above: three workgroups per CU do not
 // hide the window's round trip and the per-particle shuffle chains.  Not kept.)
-static void launch_gather_inter(hipStream_t st, float *vout, const float4 *gi, int N, int3 n, int3 support, float dV, FastDiv dsx,
-                                FastDiv dsxy, const FcmPrep &pr, bool accumulate, int perWave = 2, bool packed = false, int *ran = nullptr) {
-  // ran (uammd_fcm_probe): {UAMMD_FCM_GATHER_*, R or S, P, SZMAX} of the instantiation launched below
-  const auto note = [ran](int form, int rs, int P, int szmax) { if (ran) { ran[0] = form; ran[1] = rs; ran[2] = P; ran[3] = szmax; } };
-  // the column form where the float4 grid stays in the 256 MB Infinity Cache (C4: 39.5 -> 32.9 us; at C5, a 268 MB grid read from HBM,
-  // its six partly filled loads per particle lose to the four full ones: 126 against 112 us)
-  const size_t nodes = (size_t)n.x * n.y * n.z;
-  static const int halfMode = getenv("UAMMD_FCM_GATHER_HALF") ? atoi(getenv("UAMMD_FCM_GATHER_HALF")) : 1;   // (A/B runs: 0 off, 2 also on grids read from HBM)
-  if (packed) {  // (fcm_inter_packed: a grid read from HBM, 12 bytes per node; the float4 forms below do not apply)
-    const int rounds = (support.x * support.y * support.z + 63) / 64;
-    // (P as instantiated below: up to two rounds always two particles per wave.  It used to be 4 with option "gather_per_wave" = 4 there
-    // as well, and a grid sized for four per wave under a kernel that takes two left half of the particles ungathered — supports 3, 4, 5
-    // on a packed grid: tests/test_gpu_fcm_stages.py, test_gather_forms[packed-1-2-per-wave-4] and [packed-2-2-per-wave-4])
-    const int P = rounds <= 2 ? 2 : rounds <= 4 ? (perWave >= 4 ? 4 : 2) : 1;
-    const dim3 g((N + kGatherWaves * P - 1) / (kGatherWaves * P)), b(64 * kGatherWaves);
-#define UH_GIP(RR, PP) do { note(UAMMD_FCM_GATHER_INTER, RR, PP, 0); hipLaunchKernelGGL((k_fcm_gather_inter<RR, PP, true>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate); } while (0)
-    if (rounds <= 1) UH_GIP(1, 2); else if (rounds <= 2) UH_GIP(2, 2); else if (rounds <= 4) { if (P == 4) UH_GIP(4, 4); else UH_GIP(4, 2); } else UH_GIP(8, 1);
-#undef UH_GIP
-    return;
+// ---- fcm.hip launches what fcm_launch_choice.hpp chose -----------------------------------------------------------------------------------
+static_assert(kFcmGatherAtomic == UAMMD_FCM_GATHER_ATOMIC && kFcmGatherTile == UAMMD_FCM_GATHER_TILE && kFcmGatherPrep == UAMMD_FCM_GATHER_PREP &&
+              kFcmGatherInter == UAMMD_FCM_GATHER_INTER && kFcmGatherCol == UAMMD_FCM_GATHER_COL && kFcmGatherHalf == UAMMD_FCM_GATHER_HALF, "uammd_fcm_probe");
+template <int V> using IntC = std::integral_constant<int, V>;
+template <bool V> using BoolC = std::integral_constant<bool, V>;
+// The instantiations of the three interleaved gathers, each named once: launch(...) gets the template arguments as integral constants.
+// False: the choice names a kernel that does not exist (fcm_choose_gather never does: tests/cxx/fcm_launch_choice.cpp, G2 - G5).
+template <class Launch>
+static bool fcm_dispatch_gather_inter(const FcmGatherChoice &c, Launch &&launch) {   // k_fcm_gather_inter<R, P, PK>
+  switch ((c.packed ? 100 : 0) + 10 * c.rs + c.P) {
+    case 11: launch(IntC<1>{}, IntC<1>{}, BoolC<false>{}); return true;
+    case 12: launch(IntC<1>{}, IntC<2>{}, BoolC<false>{}); return true;
+    case 14: launch(IntC<1>{}, IntC<4>{}, BoolC<false>{}); return true;
+    case 21: launch(IntC<2>{}, IntC<1>{}, BoolC<false>{}); return true;
+    case 22: launch(IntC<2>{}, IntC<2>{}, BoolC<false>{}); return true;
+    case 24: launch(IntC<2>{}, IntC<4>{}, BoolC<false>{}); return true;
+    case 41: launch(IntC<4>{}, IntC<1>{}, BoolC<false>{}); return true;
+    case 42: launch(IntC<4>{}, IntC<2>{}, BoolC<false>{}); return true;
+    case 44: launch(IntC<4>{}, IntC<4>{}, BoolC<false>{}); return true;
+    case 81: launch(IntC<8>{}, IntC<1>{}, BoolC<false>{}); return true;
+    case 112: launch(IntC<1>{}, IntC<2>{}, BoolC<true>{}); return true;
+    case 122: launch(IntC<2>{}, IntC<2>{}, BoolC<true>{}); return true;
+    case 142: launch(IntC<4>{}, IntC<2>{}, BoolC<true>{}); return true;
+    case 144: launch(IntC<4>{}, IntC<4>{}, BoolC<true>{}); return true;
+    case 181: launch(IntC<8>{}, IntC<1>{}, BoolC<true>{}); return true;
   }
-  if (halfMode == 2 && perWave >= 0 && support.x == 6 && support.y == 6 && support.z <= 8 && nodes * sizeof(float4) < ((size_t)1 << 32)) {
-    const dim3 g((N + kGatherWaves * 2 - 1) / (kGatherWaves * 2)), b(64 * kGatherWaves);
-    if (support.z <= 6) { note(UAMMD_FCM_GATHER_HALF, 6, 2, 6); hipLaunchKernelGGL((k_fcm_gather_half<6, 6>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
-    else { note(UAMMD_FCM_GATHER_HALF, 6, 2, 8); hipLaunchKernelGGL((k_fcm_gather_half<6, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
-    return;
+  return false;
+}
+template <class Launch>
+static bool fcm_dispatch_gather_columns(const FcmGatherChoice &c, Launch &&launch) {   // k_fcm_gather_col<2, SZMAX> (S = 0), k_fcm_gather_half<S, SZMAX>
+  if (c.P != 2) return false;
+  switch (10 * c.rs + c.szmax) {
+    case 6: launch(IntC<0>{}, IntC<6>{}); return true;
+    case 8: launch(IntC<0>{}, IntC<8>{}); return true;
+    case 66: launch(IntC<6>{}, IntC<6>{}); return true;
+    case 68: launch(IntC<6>{}, IntC<8>{}); return true;
+    case 77: launch(IntC<7>{}, IntC<7>{}); return true;
+    case 78: launch(IntC<7>{}, IntC<8>{}); return true;
   }
-  if (perWave >= 0 && support.x <= 8 && support.y <= 8 && support.z <= 8 && nodes * sizeof(float4) <= ((size_t)128 << 20)) {
-    constexpr int P = 2;  // (32.9 / 33.5 / 36.4 us with 2 / 3 / 4 particles per wave at C4)
-    const dim3 g((N + kGatherWaves * P - 1) / (kGatherWaves * P)), b(64 * kGatherWaves);
-    if (support.x == 6 && support.y == 6 && halfMode != 0) {
-      if (support.z <= 6) { note(UAMMD_FCM_GATHER_HALF, 6, 2, 6); hipLaunchKernelGGL((k_fcm_gather_half<6, 6>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
-      else { note(UAMMD_FCM_GATHER_HALF, 6, 2, 8); hipLaunchKernelGGL((k_fcm_gather_half<6, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
-      return;
-    }
-    if (support.x == 7 && support.y == 7 && halfMode != 0) {
-      if (support.z <= 7) { note(UAMMD_FCM_GATHER_HALF, 7, 2, 7); hipLaunchKernelGGL((k_fcm_gather_half<7, 7>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
-      else { note(UAMMD_FCM_GATHER_HALF, 7, 2, 8); hipLaunchKernelGGL((k_fcm_gather_half<7, 8>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate); }
-      return;
-    }
-    if (support.z <= 6) { note(UAMMD_FCM_GATHER_COL, 0, 2, 6); hipLaunchKernelGGL((k_fcm_gather_col<2, 6>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate); }
-    else { note(UAMMD_FCM_GATHER_COL, 0, 2, 8); hipLaunchKernelGGL((k_fcm_gather_col<2, 8>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate); }
-    return;
+  return false;
+}
+template <int S, int SZMAX>
+static void fcm_launch_gather_columns(IntC<S>, IntC<SZMAX>, dim3 g, dim3 b, hipStream_t st, float *vout, const float4 *gi, int N, int3 n, int3 support,
+                                      float dV, const FcmPrep &pr, bool accumulate) {
+  hipLaunchKernelGGL((k_fcm_gather_half<S, SZMAX>), g, b, 0, st, vout, gi, N, n, support.z, dV, pr, accumulate);
+}
+template <int SZMAX>
+static void fcm_launch_gather_columns(IntC<0>, IntC<SZMAX>, dim3 g, dim3 b, hipStream_t st, float *vout, const float4 *gi, int N, int3 n, int3 support,
+                                      float dV, const FcmPrep &pr, bool accumulate) {
+  hipLaunchKernelGGL((k_fcm_gather_col<2, SZMAX>), g, b, 0, st, vout, gi, N, n, support, dV, pr, accumulate);
+}
+
+// what a handle's options and grid say to fcm_choose_gather (customFFT: this solve's inverse x transform writes the interleaved grid itself)
+static FcmGatherChoice fcm_gather_choice(const FCM *f, bool customFFT, bool packedGiven) {
+  return fcm_choose_gather(FcmGatherInputs{f->useTiles && !f->forceAtomicSpread, f->interGather, f->prep.tileGather, to_choice(f->kern.support),
+                                           to_choice(f->grid.cellDim), f->gatherPerWave, customFFT, packedGiven, fcm_switches()});
+}
+// The gather that `c` names.  src: the interleaved grid for the forms that read one (c.readsInterleaved), else the three planar real
+// grids with z stride zs.  d_pos: read by the atomic form only, which has no prepared stencils.
+static int fcm_run_gather(const FCM *f, const FcmGatherChoice &c, const void *src, size_t zs, const float *d_pos, const FcmPrep &pr, int N,
+                          float *vout, bool accumulate, hipStream_t st) {
+  const int3 n = f->grid.cellDim, support = f->kern.support;
+  const float dV = f->grid.cellVolume;
+  const FastDiv dsx = make_fastdiv(support.x), dsxy = make_fastdiv(support.x * support.y);
+  const dim3 gp((N + 3) / 4), g(c.readsInterleaved ? c.blocks(N) : 0), b(64 * kGatherWaves);
+  const float *planar = (const float *)src;
+  const float4 *gi = (const float4 *)src;
+  bool known = true;
+  switch (c.form) {
+    case kFcmGatherAtomic:
+      hipLaunchKernelGGL((k_fcm_ibm<false>), gp, dim3(256), 0, st, (const float4 *)d_pos, (const float4 *)nullptr, vout, (float *)planar, N, f->grid,
+                         f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, accumulate);
+      break;
+    case kFcmGatherTile:
+      hipLaunchKernelGGL(k_fcm_gather_tile, dim3(f->ntiles.x * f->ntiles.y * f->ntiles.z), dim3(256), 0, st, vout, planar, n, f->nxpad, f->planeReal,
+                         zs, support, f->ntiles, dV, dsx, dsxy, pr, accumulate);
+      break;
+    case kFcmGatherPrep:
+      hipLaunchKernelGGL(k_fcm_gather_prep, gp, dim3(256), 0, st, vout, planar, N, n, f->nxpad, f->planeReal, zs, support, dV, dsx, dsxy, pr, accumulate);
+      break;
+    case kFcmGatherInter:
+      known = fcm_dispatch_gather_inter(c, [&](auto R, auto P, auto PK) {
+        hipLaunchKernelGGL((k_fcm_gather_inter<decltype(R)::value, decltype(P)::value, decltype(PK)::value>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate);
+      });
+      break;
+    case kFcmGatherCol:
+    case kFcmGatherHalf:
+      known = (c.form == kFcmGatherHalf) == (c.rs != 0) &&
+              fcm_dispatch_gather_columns(c, [&](auto S, auto SZMAX) { fcm_launch_gather_columns(S, SZMAX, g, b, st, vout, gi, N, n, support, dV, pr, accumulate); });
+      break;
+    default: known = false;
   }
-  if (perWave < 0) perWave = -perWave;  // (test hook: a negative value asks for k_fcm_gather_inter with that many particles per wave)
-  const int rounds = (support.x * support.y * support.z + 63) / 64;
-  // (measured at C4, support 6: 47.3 / 40.2 / 40.8 us with 1 / 2 / 4 particles per wave)
-  const int P = (rounds <= 4 && perWave >= 2) ? (perWave >= 4 ? 4 : 2) : 1;
-  const dim3 g((N + kGatherWaves * P - 1) / (kGatherWaves * P)), b(64 * kGatherWaves);
-#define UH_GI(RR, PP) do { note(UAMMD_FCM_GATHER_INTER, RR, PP, 0); hipLaunchKernelGGL((k_fcm_gather_inter<RR, PP>), g, b, 0, st, vout, gi, N, n, support, dV, dsx, dsxy, pr, accumulate); } while (0)
-  if (rounds <= 1) { if (P == 4) UH_GI(1, 4); else if (P == 2) UH_GI(1, 2); else UH_GI(1, 1); }
-  else if (rounds <= 2) { if (P == 4) UH_GI(2, 4); else if (P == 2) UH_GI(2, 2); else UH_GI(2, 1); }
-  else if (rounds <= 4) { if (P == 4) UH_GI(4, 4); else if (P == 2) UH_GI(4, 2); else UH_GI(4, 1); }
-  else UH_GI(8, 1);
-#undef UH_GI
+  if (!known) { set_last_error("fcm: no gather kernel for form %d, R/S %d, P %d, SZMAX %d", c.form, c.rs, c.P, c.szmax); return -1; }
+  return 0;
+}
+
+// The tile-owned spread that `c` names, one workgroup per tile.
+template <class Launch>
+static bool fcm_dispatch_spread(const FcmSpreadChoice &c, bool slots, Launch &&launch) {   // k_fcm_spread_tile<W, SLOTS, E, SPEC>
+  if ((c.waves != 2 && c.waves != 4) || (c.edge != kTile && c.edge != kTileMax) || (c.spec && !slots)) return false;
+  // (W in {2, 4} x E in {kTile, kTileMax} x (SLOTS, SPEC) in {(false, false), (true, false), (true, true)}: twelve kernels)
+  const auto byEdge = [&](auto W, auto SLOTS, auto SPEC) {
+    if (c.edge == kTileMax) launch(W, SLOTS, IntC<kTileMax>{}, SPEC); else launch(W, SLOTS, IntC<kTile>{}, SPEC);
+  };
+  const auto byWaves = [&](auto SLOTS, auto SPEC) {
+    if (c.waves == 2) byEdge(IntC<2>{}, SLOTS, SPEC); else byEdge(IntC<4>{}, SLOTS, SPEC);
+  };
+  if (c.spec) byWaves(BoolC<true>{}, BoolC<true>{}); else if (slots) byWaves(BoolC<true>{}, BoolC<false>{}); else byWaves(BoolC<false>{}, BoolC<false>{});
+  return true;
+}
+static FcmSpreadChoice fcm_spread_choice(const FCM *f, int N, int wavesOption, bool slots, int cap, bool allowSpec) {
+  return fcm_choose_spread(FcmSpreadInputs{N, to_choice(f->ntiles), to_choice(f->kern.support), to_choice(f->tdim), wavesOption, slots, cap, allowSpec,
+                                           fcm_switches()});
+}
+static int fcm_run_spread_tile(const FCM *f, const FcmSpreadChoice &c, bool slots, float *g, size_t zs, const FcmPrep &pr, hipStream_t st) {
+  const dim3 sg(f->ntiles.x * f->ntiles.y * f->ntiles.z), sb(64 * c.waves);
+  const size_t lds = fcm_spread_lds_bytes(c, sizeof(SpEntry));
+  if (!fcm_dispatch_spread(c, slots, [&](auto W, auto SLOTS, auto E, auto SPEC) {
+        hipLaunchKernelGGL((k_fcm_spread_tile<decltype(W)::value, decltype(SLOTS)::value, decltype(E)::value, decltype(SPEC)::value>), sg, sb, lds, st, g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support,
+                           f->ntiles, pr, c.weightWords);
+      })) {
+    set_last_error("fcm: no spread kernel for %d waves, edge %d, spec %d", c.waves, c.edge, (int)c.spec);
+    return -1;
+  }
+  return 0;
 }
 
 // ---- Fourier space ---------------------------------------------------------------------------------------
@@ -1726,7 +1794,7 @@ static bool fcm_plane_fft_usable(int nx, int ny) {
   if (!ldsKnown[dev]) {
     int v = 0;
     ldsLimits[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess ? v : 0;
-    if (getenv("UAMMD_FCM_NO_PLANE_FFT")) ldsLimits[dev] = 0;
+    if (fcm_switches().noPlaneFft) ldsLimits[dev] = 0;
     ldsKnown[dev] = true;
   }
   const int ldsLimit = ldsLimits[dev];
@@ -1821,13 +1889,7 @@ static int fcm_fft_z_operator_y(FCM *f, float *g, bool haveForce, float noisePre
   return 0;
 }
 // inverse x transform of the three components: into the planar real grids in place, or into the gather's interleaved float4 grid
-// The gather's grid with 12 bytes per node: where the float4 grid would not stay in the Infinity Cache between the inverse x pass and the
-// gather (> 128 MB: the same bound launch_gather_inter uses for its cache-resident forms).  UAMMD_FCM_PACKED_INTER=0: float4 everywhere.
-static bool fcm_inter_packed(const FCM *f) {
-  static const bool on = !(getenv("UAMMD_FCM_PACKED_INTER") && atoi(getenv("UAMMD_FCM_PACKED_INTER")) == 0);
-  const size_t nodes = (size_t)f->grid.cellDim.x * f->grid.cellDim.y * f->grid.cellDim.z;
-  return on && nodes * sizeof(float4) > ((size_t)128 << 20) && f->gatherPerWave >= 0;
-}
+// (packed: the gather's grid with 12 bytes per node, FcmGatherChoice::packed)
 static int fcm_fft_inverse_x(FCM *f, float *g, float4 *inter, hipStream_t st, bool packed = false) {
   const int nx = f->grid.cellDim.x, ny = f->grid.cellDim.y, nz = f->grid.cellDim.z, nh = nx / 2;
   const int rows = std::max(1, std::min(8, 2048 / (3 * nh))), nrows = ny * nz;
@@ -1982,27 +2044,7 @@ static int fcm_prepare(FCM *f, const float *d_pos, const float *d_force, int N, 
 
 // tile-owned spreading is possible when the grid is a whole number (>= 3) of tiles per axis and a stencil only
 // reaches the adjacent tiles
-// (a particle is binned by ITS cell and its stencil reaches support / 2 (+ 1 with the shift of even supports) nodes either way: it stays
-// within the adjacent tiles when support <= 2 (T - 1)).  The tile edge T is chosen per axis: the largest divisor of the axis in 4..8
-// that satisfies this — 8 for power-of-two grids, 6 for the 108^3 grid of the PSE far field at psi = 0.5, 5 for 100, 7 for 84.  The
-// kernels' LDS / matrix layouts are sized for 8; a shorter tile leaves rows and columns unused (and unwritten).
-static bool fcm_tiles_usable(const int cells[3], const int support[3], int3 *tdim, bool only8 = false) {
-  static const bool nine = getenv("UAMMD_FCM_NO_TILE9") == nullptr;   // (A/B runs: the 9-node edge of round 6 off)
-  int T[3];
-  for (int a = 0; a < 3; ++a) {
-    T[a] = 0;
-    // 8 where it divides the axis; then 9 (the spread's second instantiation: 108, 162, 180, 198, 270 ...) before the shorter edges
-    const int order[6] = {8, 9, 7, 6, 5, 4};
-    for (int k = 0; k < (only8 ? 1 : 6); ++k) {
-      const int t = order[k];
-      if (t == 9 && !nine) continue;
-      if (cells[a] % t == 0 && cells[a] / t >= 3 && support[a] <= 2 * (t - 1)) { T[a] = t; break; }
-    }
-    if (!T[a]) return false;
-  }
-  *tdim = make_int3(T[0], T[1], T[2]);
-  return true;
-}
+// (fcm_tiles_usable, fcm_launch_choice.hpp)
 
 // ---- z-slab decomposed solver (SURVEY §8e path B; BASELINE configs[4]) ------------------------------------------
 // One rank owns nzLocal xy-planes of the real grid (plus `halo` planes each side that receive the stencils of its own
@@ -2088,7 +2130,9 @@ int uammd_fcm_create(const uammd_fcm_parameters *par, uammd_fcm **out) {
   f->kern = to_dev(par->kernel);
   fft_padded_layout(3, par->cells, &f->nxpad, &f->planeReal, &f->planeCplx);
   if (int e = f->gridBuf.reserve(sizeof(float) * 3 * f->planeReal)) { delete f; return e; }
-  f->useTiles = fcm_tiles_usable(par->cells, par->kernel.support, &f->tdim);
+  FcmInt3 tdim{8, 8, 8};
+  f->useTiles = fcm_tiles_usable(par->cells, par->kernel.support, false, fcm_switches(), &tdim);
+  f->tdim = make_int3(tdim.x, tdim.y, tdim.z);
   f->ntiles = make_int3(par->cells[0] / f->tdim.x, par->cells[1] / f->tdim.y, par->cells[2] / f->tdim.z);
   if (int e = f->fft.create(3, par->cells, f->nxpad, f->planeReal, f->planeCplx, rocfft_precision_single, 3, 3)) { delete f; return e; }
   *out = reinterpret_cast<uammd_fcm *>(f);
@@ -2206,42 +2250,14 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
   } else if (int e = fcm_prepare(f, d_pos, d_force, N, st, positionsKept, tiles, &pr, &slots)) return e;
   if (d_force && half != 2) {
     if (tiles) {
-      const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
-      const int ww = spread_weight_words(N, f->ntiles, f->kern.support, f->tdim);
-      const int sw = spread_waves(N, f->ntiles, f->kern.support, f->tdim, f->spreadWaves);
-      const int edge = spread_edge(f->tdim);
-      const dim3 sg(nt), sb(64 * sw);
-      const size_t lds = spread_lds_bytes(ww, sw, edge);
-#define UH_SPREAD(W, S, E) hipLaunchKernelGGL((k_fcm_spread_tile<W, S, E>), sg, sb, lds, st, g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles, pr, ww)
-      // (SPEC: see the kernel — two waves per tile, exactly eight source tiles, slots deep enough)
-      static const bool specOn = getenv("UAMMD_FCM_NO_SPEC") == nullptr;
-      const bool eight = (f->kern.support.x - 2 + f->tdim.x) / f->tdim.x == 1 && (f->kern.support.y - 2 + f->tdim.y) / f->tdim.y == 1 &&
-                         (f->kern.support.z - 2 + f->tdim.z) / f->tdim.z == 1;
-      // (dense tiles, four waves, 8 x 32 slots: measured at C4 with no gain — 0.1578 / 0.1580 / 0.1593 against 0.1578 / 0.1589 / 0.1594 ms —
-      // since the records' round trip hides behind the other tiles' matrix steps there; kept behind UAMMD_FCM_SPEC_DENSE=1 for A/B runs)
-      static const bool specDense = getenv("UAMMD_FCM_SPEC_DENSE") != nullptr;
-      // (the round lists up to one record per thread at once: the list and its weights must hold a workgroup's worth — capEntries >= 64 W)
-      const bool spec = specOn && slots && eight && pr.cap >= 8 * sw && ww / (3 * edge) >= 64 * sw && (sw == 2 || specDense);
+      const FcmSpreadChoice sc = fcm_spread_choice(f, N, f->spreadWaves, slots, pr.cap, true);
       if (probe) {
         if (probe->nanFill) UH_CHECK(hipMemsetD32Async((hipDeviceptr_t)g, 0x7fc00000, 3 * f->planeReal, st));   // (the kernel has no memset: it owns every node)
-        const int said[] = {UAMMD_FCM_PROBE_SPREAD, f->prep.lastPreparation(), 1, sw, slots, edge, spec, f->tdim.x, f->tdim.y, f->tdim.z,
-                            std::min(64 * sw, ww / (3 * edge)), pr.cap, f->ranPrepLanes, f->ranPrepKernel};
+        const int said[] = {UAMMD_FCM_PROBE_SPREAD, f->prep.lastPreparation(), 1, sc.waves, slots, sc.edge, sc.spec, f->tdim.x, f->tdim.y, f->tdim.z,
+                            sc.listEntries, pr.cap, f->ranPrepLanes, f->ranPrepKernel};
         std::copy(said, said + 14, probe->info);
       }
-#define UH_SPREAD_SPEC(W, E) hipLaunchKernelGGL((k_fcm_spread_tile<W, true, E, true>), sg, sb, lds, st, g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles, pr, ww)
-      if (spec) {
-        if (sw == 2) { if (edge == kTileMax) UH_SPREAD_SPEC(2, kTileMax); else UH_SPREAD_SPEC(2, kTile); }
-        else { if (edge == kTileMax) UH_SPREAD_SPEC(4, kTileMax); else UH_SPREAD_SPEC(4, kTile); }
-      }
-      else if (edge == kTileMax) {
-        if (sw == 2) { if (slots) UH_SPREAD(2, true, kTileMax); else UH_SPREAD(2, false, kTileMax); }
-        else { if (slots) UH_SPREAD(4, true, kTileMax); else UH_SPREAD(4, false, kTileMax); }
-      } else {
-        if (sw == 2) { if (slots) UH_SPREAD(2, true, kTile); else UH_SPREAD(2, false, kTile); }
-        else { if (slots) UH_SPREAD(4, true, kTile); else UH_SPREAD(4, false, kTile); }
-      }
-#undef UH_SPREAD
-#undef UH_SPREAD_SPEC
+      if (int e = fcm_run_spread_tile(f, sc, slots, g, zs, pr, st)) return e;
     } else {
       if (probe) probe->info[0] = UAMMD_FCM_PROBE_SPREAD;   // (atomic: no preparation, no tiles — the rest stays 0)
       UH_CHECK(hipMemsetAsync(g, 0, sizeof(float) * 3 * f->planeReal, st));
@@ -2279,38 +2295,26 @@ static int fcm_displacements_impl(uammd_fcm *h, const float *d_pos, const float 
     if (stage == 1) { UH_CHECK(hipGetLastError()); return 0; }
     if (int e = f->fft.inverse(g)) return e;
   }
-  const bool interPath = tiles && f->interGather && !(tiles && (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6) && f->prep.tileGather);
-  if (custom && !interPath) { if (int e = fcm_fft_inverse_x(f, g, nullptr, st)) return e; }
-  const bool smallSupport = f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6;
+  const bool given = probe && probe->packed;   // (the caller's packed grid instead of the handle's)
+  const FcmGatherChoice gc = fcm_gather_choice(f, custom, given);
+  if (custom && !gc.readsInterleaved) { if (int e = fcm_fft_inverse_x(f, g, nullptr, st)) return e; }
   const bool accumulate = f->accumulate || (probe && probe->accumulate);
-  int ran[4] = {tiles ? (smallSupport && f->prep.tileGather ? UAMMD_FCM_GATHER_TILE : UAMMD_FCM_GATHER_PREP) : UAMMD_FCM_GATHER_ATOMIC, 0, 0, 0};
-  if (tiles && smallSupport && f->prep.tileGather)
-    hipLaunchKernelGGL(k_fcm_gather_tile, dim3(f->ntiles.x * f->ntiles.y * f->ntiles.z), bp, 0, st, d_linearVelocity,
-                       (const float *)g, f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles,
-                       f->grid.cellVolume, dsx, dsxy, pr, accumulate);
-  else if (tiles && f->interGather) {
+  const void *src = g;
+  if (gc.readsInterleaved && given) src = probe->inter;
+  else if (gc.readsInterleaved) {
     const size_t nodes = (size_t)f->grid.cellDim.x * f->grid.cellDim.y * f->grid.cellDim.z;
-    const bool given = probe && probe->packed;   // (the caller's packed grid instead of the handle's)
-    if (!given)
-      if (int e = f->interBuf.reserve(sizeof(float4) * nodes)) return e;
-    const bool packed = given || (custom && fcm_inter_packed(f));
-    if (given) {
-    } else if (custom) {  // the inverse x transform writes the interleaved grid itself
-      if (int e = fcm_fft_inverse_x(f, g, (float4 *)f->interBuf.ptr, st, packed)) return e;
+    if (int e = f->interBuf.reserve(sizeof(float4) * nodes)) return e;
+    if (custom) {  // the inverse x transform writes the interleaved grid itself
+      if (int e = fcm_fft_inverse_x(f, g, (float4 *)f->interBuf.ptr, st, gc.packed)) return e;
     } else
       hipLaunchKernelGGL(k_fcm_interleave, dim3((unsigned)((nodes + 255) / 256)), bp, 0, st, (const float *)g, f->grid.cellDim, f->nxpad,
                          f->planeReal, zs, (float4 *)f->interBuf.ptr);
-    launch_gather_inter(st, d_linearVelocity, given ? probe->inter : (const float4 *)f->interBuf.ptr, N, f->grid.cellDim, f->kern.support,
-                        f->grid.cellVolume, dsx, dsxy, pr, accumulate, f->gatherPerWave, packed, ran);
-  } else if (tiles)
-    hipLaunchKernelGGL(k_fcm_gather_prep, gp, bp, 0, st, d_linearVelocity, (const float *)g, N, f->grid.cellDim, f->nxpad,
-                       f->planeReal, zs, f->kern.support, f->grid.cellVolume, dsx, dsxy, pr, accumulate);
-  else
-    hipLaunchKernelGGL((k_fcm_ibm<false>), gp, bp, 0, st, (const float4 *)d_pos, (const float4 *)nullptr,
-                       d_linearVelocity, g, N, f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, accumulate);
+    src = f->interBuf.ptr;
+  }
+  if (int e = fcm_run_gather(f, gc, src, zs, d_pos, pr, N, d_linearVelocity, accumulate, st)) return e;
   UH_CHECK(hipGetLastError());
   if (probe && stage == kStageGather) {
-    const int said[] = {UAMMD_FCM_PROBE_GATHER, f->prep.lastPreparation(), ran[0], ran[1], ran[2], ran[3], ran[0] == UAMMD_FCM_GATHER_INTER && probe->packed,
+    const int said[] = {UAMMD_FCM_PROBE_GATHER, f->prep.lastPreparation(), gc.form, gc.rs, gc.P, gc.szmax, gc.form == kFcmGatherInter && probe->packed,
                         accumulate, 0, 0, 0, 0, f->ranPrepLanes, f->ranPrepKernel};
     std::copy(said, said + 14, probe->info);
   }
@@ -2342,8 +2346,7 @@ int uammd_fcm_probe(uammd_fcm *h, int stage, const float *d_pos, const float *d_
     probe.packed = (flags & UAMMD_FCM_PROBE_PACKED) != 0;
     probe.accumulate = (flags & UAMMD_FCM_PROBE_ACCUMULATE) != 0;
     if (!d_linearVelocity || (probe.packed ? !d_inter : !d_grid)) { set_last_error("uammd_fcm_probe: the gather needs d_linearVelocity and a grid"); return -1; }
-    const bool small = f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6;
-    if (probe.packed && !(f->useTiles && !f->forceAtomicSpread && f->interGather && !(small && f->prep.tileGather))) {
+    if (probe.packed && !fcm_gather_choice(f, false, true).readsInterleaved) {
       set_last_error("uammd_fcm_probe: the handle's options do not select the interleaved gather, which is the one that reads a packed grid");
       return -2;
     }
@@ -2422,12 +2425,8 @@ int uammd_fcm_set_option(uammd_fcm *h, const char *name, int value) {
   if (std::string(name) == "spread_waves") { reinterpret_cast<FCM *>(h)->spreadWaves = value; return 0; }
   if (std::string(name) == "gather_per_wave") { reinterpret_cast<FCM *>(h)->gatherPerWave = value; return 0; }
   if (std::string(name) == "tile_gather") {
-    // (the staged window is loaded in aligned x pairs and is 16 nodes wide: an even tile edge along x, edge + support - 1 <= 16; elsewhere the
-    // option is accepted and the global gather runs)
     FCM *f = reinterpret_cast<FCM *>(h);
-    const bool fits = f->tdim.x % 2 == 0 && f->tdim.x + f->kern.support.x - 1 <= 16 && f->tdim.y + f->kern.support.y - 1 <= 16 &&
-                      f->tdim.z + f->kern.support.z - 1 <= 16;
-    f->prep.tileGather = value != 0 && fits;
+    f->prep.tileGather = value != 0 && fcm_tile_gather_fits(to_choice(f->tdim), to_choice(f->kern.support));
     return 0;
   }
   if (std::string(name) == "interleaved_gather") { reinterpret_cast<FCM *>(h)->interGather = value != 0; return 0; }
@@ -2481,7 +2480,9 @@ int uammd_fcm_slab_create(const uammd_fcm_parameters *par, int nzLocal, int z0, 
   f->kern = to_dev(par->kernel);
   f->nxpad = 2 * s->nkx;
   f->planeReal = (size_t)f->nxpad * lc[1];  // component stride of the interleaved-plane layout
-  f->useTiles = fcm_tiles_usable(lc, par->kernel.support, &f->tdim, true);  // (the slab window's halo is a whole number of 8-node tiles)
+  FcmInt3 tdim{8, 8, 8};
+  f->useTiles = fcm_tiles_usable(lc, par->kernel.support, true, fcm_switches(), &tdim);  // (the slab window's halo is a whole number of 8-node tiles)
+  f->tdim = make_int3(tdim.x, tdim.y, tdim.z);
   f->ntiles = make_int3(lc[0] / f->tdim.x, lc[1] / f->tdim.y, lc[2] / f->tdim.z);
   if (int e = fcm_slab_make_plans(s)) { delete s; return e; }
   *out = reinterpret_cast<uammd_fcm_slab *>(s);
@@ -2518,16 +2519,9 @@ int uammd_fcm_slab_spread(uammd_fcm_slab *h, const float *d_posLocal, const floa
   bool slots = false;
   if (int e = fcm_prepare(f, d_posLocal, d_force, N, st, false, tiles, &pr, &slots)) return e;
   if (tiles) {
-    if (d_force) {
-      const int nt = f->ntiles.x * f->ntiles.y * f->ntiles.z;
-      const int ww = spread_weight_words(N, f->ntiles, f->kern.support, f->tdim);
-      if (slots)
-        hipLaunchKernelGGL((k_fcm_spread_tile<4, true>), dim3(nt), dim3(256), spread_lds_bytes(ww), st, d_grid, f->grid.cellDim, f->nxpad,
-                           f->planeReal, zs, f->kern.support, f->ntiles, pr, ww);
-      else
-        hipLaunchKernelGGL((k_fcm_spread_tile<4, false>), dim3(nt), dim3(256), spread_lds_bytes(ww), st, d_grid, f->grid.cellDim, f->nxpad,
-                           f->planeReal, zs, f->kern.support, f->ntiles, pr, ww);
-    }
+    // (the slab: always four waves per tile, no speculative round; its tiles have 8 nodes per axis, so this is k_fcm_spread_tile<4, slots, kTile, false>)
+    if (d_force)
+      if (int e = fcm_run_spread_tile(f, fcm_spread_choice(f, N, 4, slots, pr.cap, false), slots, d_grid, zs, pr, st)) return e;
   } else if (d_force) {
     const FastDiv dsx = make_fastdiv(f->kern.support.x), dsxy = make_fastdiv(f->kern.support.x * f->kern.support.y);
     hipLaunchKernelGGL((k_fcm_ibm<true>), dim3((N + 3) / 4), dim3(256), 0, st, (const float4 *)d_posLocal,
@@ -2548,29 +2542,19 @@ int uammd_fcm_slab_gather(uammd_fcm_slab *h, const float *d_posLocal, int N, con
   FCM *f = &s->loc;
   hipStream_t st = (hipStream_t)stream;
   const size_t zs = 3 * f->planeReal;
-  const FastDiv dsx = make_fastdiv(f->kern.support.x), dsxy = make_fastdiv(f->kern.support.x * f->kern.support.y);
   const bool tiles = f->useTiles && !f->forceAtomicSpread;
-  if (tiles) {
-    if (f->prep.compactCapacity() < N) { set_last_error("uammd_fcm_slab_gather: call uammd_fcm_slab_spread with these positions first"); return -3; }
-    const FcmPrep pr = fcm_prep_view(f, false, 0, nullptr);
-    if (f->kern.support.x <= 6 && f->kern.support.y <= 6 && f->kern.support.z <= 6 && f->prep.tileGather)
-      hipLaunchKernelGGL(k_fcm_gather_tile, dim3(f->ntiles.x * f->ntiles.y * f->ntiles.z), dim3(256), 0, st, d_vel, d_grid,
-                         f->grid.cellDim, f->nxpad, f->planeReal, zs, f->kern.support, f->ntiles, f->grid.cellVolume, dsx, dsxy,
-                         pr, f->accumulate);
-    else if (f->interGather) {
-      const size_t nodes = (size_t)f->grid.cellDim.x * f->grid.cellDim.y * f->grid.cellDim.z;
-      if (int e = f->interBuf.reserve(sizeof(float4) * nodes)) return e;
-      hipLaunchKernelGGL(k_fcm_interleave, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, st, d_grid, f->grid.cellDim,
-                         f->nxpad, f->planeReal, zs, (float4 *)f->interBuf.ptr);
-      launch_gather_inter(st, d_vel, (const float4 *)f->interBuf.ptr, N, f->grid.cellDim, f->kern.support, f->grid.cellVolume, dsx, dsxy,
-                          pr, f->accumulate, f->gatherPerWave);
-    } else
-      hipLaunchKernelGGL(k_fcm_gather_prep, dim3((N + 3) / 4), dim3(256), 0, st, d_vel, d_grid, N, f->grid.cellDim, f->nxpad,
-                         f->planeReal, zs, f->kern.support, f->grid.cellVolume, dsx, dsxy, pr, f->accumulate);
-  } else {
-    hipLaunchKernelGGL((k_fcm_ibm<false>), dim3((N + 3) / 4), dim3(256), 0, st, (const float4 *)d_posLocal,
-                       (const float4 *)nullptr, d_vel, (float *)d_grid, N, f->grid, f->nxpad, f->planeReal, zs, f->kern, dsx, dsxy, false);
+  if (tiles && f->prep.compactCapacity() < N) { set_last_error("uammd_fcm_slab_gather: call uammd_fcm_slab_spread with these positions first"); return -3; }
+  // (the slab's only option is "atomic_spread": tileGather = false and interGather = true, so the forms are atomic, inter, col and half)
+  const FcmGatherChoice gc = fcm_gather_choice(f, false, false);
+  const void *src = d_grid;
+  if (gc.readsInterleaved) {
+    const size_t nodes = (size_t)f->grid.cellDim.x * f->grid.cellDim.y * f->grid.cellDim.z;
+    if (int e = f->interBuf.reserve(sizeof(float4) * nodes)) return e;
+    hipLaunchKernelGGL(k_fcm_interleave, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, st, d_grid, f->grid.cellDim, f->nxpad, f->planeReal, zs,
+                       (float4 *)f->interBuf.ptr);
+    src = f->interBuf.ptr;
   }
+  if (int e = fcm_run_gather(f, gc, src, zs, d_posLocal, tiles ? fcm_prep_view(f, false, 0, nullptr) : FcmPrep{}, N, d_vel, f->accumulate, st)) return e;
   UH_CHECK(hipGetLastError());
   return 0;
 }
@@ -2733,12 +2717,9 @@ int uammd_fcm_slab_gather_inter(uammd_fcm_slab *h, const float *d_posLocal, int 
     set_last_error("uammd_fcm_slab_gather_inter: needs the tile-prepared stencils of uammd_fcm_slab_spread");
     return -3;
   }
-  const FastDiv dsx = make_fastdiv(f->kern.support.x), dsxy = make_fastdiv(f->kern.support.x * f->kern.support.y);
-  FcmPrep pr{(int4 *)f->prepOrigin.ptr, (float *)f->prepWeights.ptr, (float4 *)f->prepSorted.ptr, (int *)f->prepTileOf.ptr,
-             (int *)f->prepRank.ptr, (int *)f->prepTileCount.ptr, (int *)f->prepTileStart.ptr,
-             f->kern.support.x + f->kern.support.y + f->kern.support.z, f->tdim};
-  launch_gather_inter((hipStream_t)stream, d_vel, (const float4 *)d_inter, N, f->grid.cellDim, f->kern.support, f->grid.cellVolume, dsx,
-                      dsxy, pr, f->accumulate);
+  // (tiles are on, tileGather = false and interGather = true on the slab: one of the forms that read the float4 window)
+  if (int e = fcm_run_gather(f, fcm_gather_choice(f, false, false), d_inter, 0, nullptr, fcm_prep_view(f, false, 0, nullptr), N, d_vel, f->accumulate,
+                             (hipStream_t)stream)) return e;
   UH_CHECK(hipGetLastError());
   return 0;
 }

@@ -66,7 +66,7 @@ struct FcmUpdatePlan : FcmStepPrepPlan {  // (the base: only with kFcmUpdateStep
 class FcmPrepState {
  public:
   // options (uammd_fcm_set_option)
-  bool slots = !(getenv("UAMMD_FCM_SLOTS") && atoi(getenv("UAMMD_FCM_SLOTS")) == 0);  // "slots" (environment: A/B runs of programs that set no options)
+  bool slots = true;         // "slots" (handle creation starts it from FcmSwitches::slots: A/B runs of programs that set no options)
   bool binAhead = true;      // "bin_ahead": the step's update kernel also prepares the next solve
   // "slot_refresh": after so many slot-layout preparations in a row the next one is refused, so that a sorted solve renews the entries'
   // order (it keeps the gather's windows local).  In a run of vouching steps the refusal meets the update: it bins instead, the solve
