@@ -191,6 +191,24 @@ def test_host_tables_under_the_sanitizers(tmp_path):
     assert seen == 100000 + 2000 + g["nx"] * g["ny"] - 1
 
 
+def test_shared_slab_tables_under_the_sanitizers(tmp_path):
+    """tests/cxx/dp_slab_tables.cpp, a stand-alone program over csrc/dp_slab_host.hpp (the tables this solver shares with the doubly
+    periodic Poisson solver), built with the address and undefined-behaviour sanitizers: they stay silent and every check of the program
+    holds (the Clenshaw-Curtis weights, mirror, wave_vector against the formula it replaced, the boundary factors).  The header is
+    plain C++: no HIP include."""
+    header = os.path.join(ROOT, "uammd_amd", "csrc", "dp_slab_host.hpp")
+    src = open(header).read()
+    assert "#include <hip" not in src and "hipStream_t" not in src and "__device__" not in src
+    exe = str(tmp_path / "dp_slab_tables")
+    r = subprocess.run(["g++", "-std=c++14", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra",
+                        "-Werror", os.path.join(HERE, "cxx", "dp_slab_tables.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "dp_slab tables ok" in r.stdout and "FAILED" not in r.stdout
+
+
 # ------------------------------------------------------------------------------------------------- 6. ABI and surfaces
 SYMBOLS = ["uammd_dpstokes_" + n for n in ("create", "destroy", "mdot", "average_velocity", "fluid_cheb", "outside_count", "set_option",
                                            "stage_times", "integrator_create", "integrator_destroy", "integrator_step",

@@ -4,8 +4,9 @@ tests/dpstokes_ref.py.
 Bars.  Double: 1e-10 of the largest |value| of each output (the bar of section 17).  Float: 4 x the error of the restatement run in
 float32 against itself in float64 on the same input (the rule of sections 16 and 17).
 
-Shapes, all with w = 6, beta = 1.714 w, alpha = w / 2:
+Shapes, with w = 6 unless said otherwise, beta = 1.714 w, alpha = w / 2:
   A  12 x 14 x 19, (Lx, Ly, H) = (8, 9, 6): even sizes, nx != ny
+  A10  shape A with w = 10: a footprint of 100 columns, so the gather's second column per lane runs (w = 6 only ever runs the first)
   B  15 x 12 x 22, (10, 8, 7): an odd size, so no unpaired index in x
   C  25 x 25 x 39, (16, 16, 16), viscosity 1 / 6 pi: the grid of the reference's periodicity test
 Particles: uniform in the slab and beyond the primary cell in x and y; from four particles on, one on each wall and one within a
@@ -33,8 +34,10 @@ SHAPES = {
     "B": dict(nx=15, ny=12, nz=22, viscosity=1.3, Lx=10.0, Ly=8.0, H=7.0),
     "C": dict(nx=25, ny=25, nz=39, viscosity=1 / (6 * math.pi), Lx=16.0, Ly=16.0, H=16.0),
 }
+SHAPES["A10"] = SHAPES["A"]
+WIDTH = {"A10": 10.0}
 CASES = [("A", 65, "none"), ("A", 65, "bottom"), ("A", 65, "slit"), ("B", 300, "slit"), ("B", 2, "bottom"), ("B", 1, "none"),
-         ("C", 300, "slit"), ("C", 65, "bottom"), ("C", 2, "none")]
+         ("C", 300, "slit"), ("C", 65, "bottom"), ("C", 2, "none"), ("A10", 65, "slit")]
 REALS = ["double", "float"]
 
 
@@ -52,7 +55,7 @@ def particles(shape, n, seed=7):
     rng = np.random.default_rng(seed)
     pos = np.stack([rng.uniform(-s["Lx"], s["Lx"], n), rng.uniform(-s["Ly"], s["Ly"], n), rng.uniform(-0.5 * s["H"], 0.5 * s["H"], n)], axis=1)
     force = rng.normal(0, 1, (n, 3))
-    reach = 0.5 * W * min(s["Lx"] / s["nx"], s["Ly"] / s["ny"])
+    reach = 0.5 * WIDTH.get(shape, W) * min(s["Lx"] / s["nx"], s["Ly"] / s["ny"])
     if n >= 4:
         pos[0, 2], pos[1, 2] = 0.5 * s["H"], -0.5 * s["H"]
         pos[2, 2], pos[3, 2] = 0.5 * s["H"] - 0.3 * reach, -0.5 * s["H"] + 0.6 * reach
@@ -62,7 +65,8 @@ def particles(shape, n, seed=7):
 
 
 def parameters(shape, mode):
-    return dr.Parameters(w=W, beta=1.714 * W, alpha=0.5 * W, mode=mode, **SHAPES[shape])
+    w = WIDTH.get(shape, W)
+    return dr.Parameters(w=w, beta=1.714 * w, alpha=0.5 * w, mode=mode, **SHAPES[shape])
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,7 +84,8 @@ def reference(shape, n, mode, real):
 def product(shape, mode, real, cls=None, **kw):
     import uammd_amd as hip
     cls = cls or hip.DPStokes
-    par = cls.Parameters(w=W, beta=(1.714 * W, -1.0, -1.0), alpha=0.5 * W, mode=mode, **SHAPES[shape], **kw)
+    w = WIDTH.get(shape, W)
+    par = cls.Parameters(w=w, beta=(1.714 * w, -1.0, -1.0), alpha=0.5 * w, mode=mode, **SHAPES[shape], **kw)
     return cls(par, real=_torch(real)) if cls is hip.DPStokes else cls(None, par, real=_torch(real))
 
 

@@ -24,8 +24,7 @@
 //    exponent <= k He); the handle's z pass takes it to Chebyshev space; k_dpp_assemble adds it and forms the four components.
 // A particle with |z| > H/2 (or a non-finite coordinate) is never spread, gathered or used as a neighbour and receives nothing; it is
 // counted.  The reference has no such guard.
-#include "celllist.hpp"
-#include "cheb_grid.hpp"
+#include "dp_slab.hpp"
 #include "../../include/uammd/device/BVP.hip.hpp"
 
 #include <algorithm>
@@ -37,15 +36,9 @@
 
 namespace uammd_hip {
 
-template <class U> struct VecOf;
-template <> struct VecOf<float> { using T2 = float2; using T4 = float4; };
-template <> struct VecOf<double> { using T2 = double2; using T4 = double4; };
-
 namespace dpp {
-constexpr int kNear = 1, kTop = 2, kBottom = 4, kOutside = 8;
-constexpr int kMaxSupport = 16;  // the gather keeps ceil(support^2 / 64) <= 4 columns per lane
-constexpr int kStages = 13;      // uammd_dppoisson_stage_times: classify, spread, forward, solve, correction, 2 z passes, assemble, 2 inverses, gather, list, near
-constexpr int kTile = 8;         // the owner spread's block: kTile x kTile nodes x kTile planes per wave
+constexpr int kNear = 1, kTop = 2, kBottom = 4, kOutside = dp::kOutside;
+constexpr int kStages = 13;  // uammd_dppoisson_stage_times: classify, spread, forward, solve, correction, 2 z passes, assemble, 2 inverses, gather, list, near
 
 struct Host {  // everything create() works out before it touches the device
   double split = 0, gt = 0, He = 0, Htot = 0, h = 0, hy = 0, rcut = 0, rmax = 0, kmax = 0, thetaTop = 0, thetaBot = 0;
@@ -53,8 +46,6 @@ struct Host {  // everything create() works out before it touches the device
   bool metTop = false, metBot = false;
 };
 }  // namespace dpp
-
-template <class U> UH_D U bcast(U v, int lane) { return __shfl(v, lane, 64); }
 
 template <class U> struct NearTable {
   const typename VecOf<U>::T2 *table;  // (potential, field factor) over r^2
@@ -73,24 +64,18 @@ __global__ __launch_bounds__(256) void k_dpp_classify(const typename VecOf<U>::T
   if (active) {
     const typename VecOf<U>::T4 p = pos[i];
     const U q = charge[i];
-    const bool finite = (p.x - p.x == U(0)) && (p.y - p.y == U(0)) && (p.z - p.z == U(0));
     typename VecOf<U>::T4 r;
+    r.x = r.y = r.z = r.w = U(0);
     int4 c = make_int4(0, 0, 0, 0);
-    if (!finite || !(abs_(p.z) <= half)) {
+    if (!dp_place(g, p.x, p.y, p.z, half, r, c)) {
       flags = dpp::kOutside;
-      r.x = r.y = r.z = r.w = U(0);
     } else {
-      r.x = ChebGrid<U>::fold(p.x, g.Lx);
-      r.y = ChebGrid<U>::fold(p.y, g.Ly);
-      r.z = p.z;
       r.w = q;
       if (abs_(half - abs_(p.z)) <= threshold) {  // spreadInterp.cuh:109-132
         flags = dpp::kNear;
         if (abs_(half - p.z) <= threshold) flags |= dpp::kTop;
         if (abs_(-half - p.z) <= threshold) flags |= dpp::kBottom;
       }
-      c.x = g.leftmost_x(r.x);
-      c.y = g.leftmost_y(r.y);
     }
     c.z = flags;
     rec[i] = r;
@@ -110,124 +95,80 @@ __global__ __launch_bounds__(256) void k_dpp_classify(const typename VecOf<U>::T
   }
 }
 
-// ---- (2, 3) the spread, owner-computes ---------------------------------------------------------------------------------------------
-template <class U> UH_D bool dpp_ring_overlap(int first, int width, int tile0, int n) {  // [first, first + width) against [tile0, tile0 + kTile) mod n
-  int d = tile0 - first;
-  d = d < 0 ? d + n : (d >= n ? d - n : d);
-  return d < width || n - d < dpp::kTile;
-}
-
+// ---- (2, 3) the spread, owner-computes (the tile and the scan: DpTile) ----------------------------------------------------------------
 template <class U>
 __global__ __launch_bounds__(64) void k_dpp_spread_owner(const typename VecOf<U>::T4 *__restrict__ rec, const int4 *__restrict__ cellrec, int N,
                                                          ChebGrid<U> g, U half, U ratioTop, U ratioBot, typename VecOf<U>::T2 *__restrict__ out) {
-  constexpr int T = dpp::kTile;
-  const int lane = threadIdx.x;
-  const int tilesX = (g.nx + T - 1) / T;
-  const int tx0 = (int)(blockIdx.x % tilesX) * T, ty0 = (int)(blockIdx.x / tilesX) * T, p0 = (int)blockIdx.y * T;
-  const int ni = tx0 + (lane & (T - 1)), nj = ty0 + (lane >> 3);
-  const bool nodeOK = ni < g.nx && nj < g.ny;
-  const int last = g.nz - 1;
-  const U zTop = g.zplane[p0], zBottom = g.zplane[min(p0 + T - 1, last)];  // the block's planes span [zBottom, zTop]
-  const U zMine = g.zplane[min(p0 + (lane & (T - 1)), last)];               // lanes 0-23 evaluate (source, plane) = (lane / 8, lane % 8)
-  const bool planeMine = p0 + (lane & (T - 1)) <= last;
+  constexpr int T = dp::kTile;
+  const DpTile<U, ChebGrid<U>> tile(g);
+  const int lane = tile.lane;
   U accR[T], accI[T];
 #pragma unroll
   for (int p = 0; p < T; ++p) accR[p] = accI[p] = U(0);
-  for (int base = 0; base < N; base += 64) {
-    const int a = base + lane;
-    typename VecOf<U>::T4 r;
-    r.x = r.y = r.z = r.w = U(0);
-    int4 c = make_int4(0, 0, dpp::kOutside, 0);
-    bool hit = false;
-    if (a < N) {
-      c = cellrec[a];
-      r = rec[a];
-      if (!(c.z & dpp::kOutside)) {
-        auto reach = [&](U zs) { return zs - g.rcut <= zTop && zs + g.rcut >= zBottom; };
-        const bool oz = reach(r.z) || ((c.z & dpp::kTop) && reach(U(2) * half - r.z)) || ((c.z & dpp::kBottom) && reach(U(-2) * half - r.z));
-        hit = oz && dpp_ring_overlap<U>(c.x, g.support, tx0, g.nx) && dpp_ring_overlap<U>(c.y, g.support, ty0, g.ny);
-      }
-    }
-    unsigned long long m = __ballot(hit);
-    while (m) {  // the hits of this batch, in index order (wave-uniform)
-      const int l = __builtin_ctzll(m);
-      m &= m - 1;
-      const U px = bcast(r.x, l), py = bcast(r.y, l), pz = bcast(r.z, l), pq = bcast(r.w, l);
-      const int x0 = __shfl(c.x, l, 64), y0 = __shfl(c.y, l, 64), fl = __shfl(c.z, l, 64);
-      const int ii = ChebGrid<U>::wrap(ni - x0, g.nx), jj = ChebGrid<U>::wrap(nj - y0, g.ny);
-      U wxy = U(0);
-      if (nodeOK && ii < g.support && jj < g.support) wxy = g.weight_x(px, ni) * g.weight_y(py, nj);
-      U wl = U(0);
-      {
-        const int src = lane >> 3;
-        U zs = pz, qs = -pq;  // every spread carries -q (spreadInterp.cuh:428-434); an image's charge is -q ratio, so it spreads +q ratio
-        bool on = src == 0;
-        if (src == 1) { zs = U(2) * half - pz; qs = pq * ratioTop; on = (fl & dpp::kTop) != 0; }
-        if (src == 2) { zs = U(-2) * half - pz; qs = pq * ratioBot; on = (fl & dpp::kBottom) != 0; }
-        if (on && planeMine && src < 3) wl = qs * g.phi(zs - zMine);
-      }
-      const bool nearWall = (fl & dpp::kNear) != 0;
+  typename VecOf<U>::T4 r;
+  int4 c;
+  tile.scan(
+      N,
+      [&](int a) {
+        r.x = r.y = r.z = r.w = U(0);
+        c = make_int4(0, 0, dpp::kOutside, 0);
+        if (a >= N) return false;
+        c = cellrec[a];
+        r = rec[a];
+        if (c.z & dpp::kOutside) return false;
+        const bool oz = tile.touches_z(g, r.z) || ((c.z & dpp::kTop) && tile.touches_z(g, U(2) * half - r.z)) ||
+                        ((c.z & dpp::kBottom) && tile.touches_z(g, U(-2) * half - r.z));
+        return oz && tile.touches_xy(g, c);
+      },
+      [&](int l) {
+        const U px = bcast(r.x, l), py = bcast(r.y, l), pz = bcast(r.z, l), pq = bcast(r.w, l);
+        const int x0 = __shfl(c.x, l, 64), y0 = __shfl(c.y, l, 64), fl = __shfl(c.z, l, 64);
+        const U wxy = tile.wxy(g, px, py, x0, y0);
+        U wl = U(0);
+        {  // lanes 0-23 evaluate (source, plane) = (lane / 8, lane % 8)
+          const int src = lane >> 3;
+          U zs = pz, qs = -pq;  // every spread carries -q (spreadInterp.cuh:428-434); an image's charge is -q ratio, so it spreads +q ratio
+          bool on = src == 0;
+          if (src == 1) { zs = U(2) * half - pz; qs = pq * ratioTop; on = (fl & dpp::kTop) != 0; }
+          if (src == 2) { zs = U(-2) * half - pz; qs = pq * ratioBot; on = (fl & dpp::kBottom) != 0; }
+          if (on && tile.planeOK && src < 3) wl = qs * g.weight_z(zs, tile.zMine);
+        }
+        const bool nearWall = (fl & dpp::kNear) != 0;
 #pragma unroll
-      for (int p = 0; p < T; ++p) {
-        const U w0 = bcast(wl, p), w1 = bcast(wl, T + p), w2 = bcast(wl, 2 * T + p);
-        if (nearWall) accR[p] += wxy * w0;
-        else accI[p] += wxy * w0;
-        accI[p] += wxy * w1;
-        accI[p] += wxy * w2;
-      }
-    }
-  }
-  if (!nodeOK) return;
-  const size_t plane = (size_t)g.nx * g.ny, node = (size_t)nj * g.nx + ni;
+        for (int p = 0; p < T; ++p) {
+          const U w0 = bcast(wl, p), w1 = bcast(wl, T + p), w2 = bcast(wl, 2 * T + p);
+          if (nearWall) accR[p] += wxy * w0;
+          else accI[p] += wxy * w0;
+          accI[p] += wxy * w1;
+          accI[p] += wxy * w2;
+        }
+      });
+  if (!tile.nodeOK) return;
 #pragma unroll
   for (int p = 0; p < T; ++p)
-    if (p0 + p <= last) {
+    if (tile.has_plane(p)) {
       typename VecOf<U>::T2 v;
       v.x = accR[p];
       v.y = accI[p];
-      out[node + plane * (size_t)(p0 + p)] = v;
+      out[tile.at(g, p)] = v;
     }
 }
 
-// the cross-check: a lane per particle, atomic adds into a zeroed grid
-template <class U>
-__global__ __launch_bounds__(64) void k_dpp_spread_simple(const typename VecOf<U>::T4 *__restrict__ rec, const int4 *__restrict__ cellrec, int N,
-                                                          ChebGrid<U> g, U half, U ratioTop, U ratioBot, U *__restrict__ out) {
-  const int a = blockIdx.x * 64 + threadIdx.x;
-  if (a >= N) return;
-  const int4 c = cellrec[a];
-  if (c.z & dpp::kOutside) return;
-  const typename VecOf<U>::T4 r = rec[a];
-  const size_t plane = (size_t)g.nx * g.ny;
-  for (int src = 0; src < 3; ++src) {
-    U zs = r.z, qs = -r.w;
-    if (src == 1) { if (!(c.z & dpp::kTop)) continue; zs = U(2) * half - r.z; qs = r.w * ratioTop; }
-    if (src == 2) { if (!(c.z & dpp::kBottom)) continue; zs = U(-2) * half - r.z; qs = r.w * ratioBot; }
-    const int comp = (src == 0 && (c.z & dpp::kNear)) ? 0 : 1;
-    int lo, hi;
-    g.plane_range(zs, lo, hi);
-    for (int k = lo; k <= hi; ++k) {
-      const U wz = qs * g.phi(zs - g.zplane[k]);
-      if (wz == U(0)) continue;
-      for (int jj = 0; jj < g.support; ++jj) {
-        const int j = ChebGrid<U>::wrap(c.y + jj, g.ny);
-        const U wy = g.weight_y(r.y, j);
-        for (int ii = 0; ii < g.support; ++ii) {
-          const int i = ChebGrid<U>::wrap(c.x + ii, g.nx);
-          const U w = (g.weight_x(r.x, i) * wy) * wz;
-          if (w != U(0)) unsafeAtomicAdd(&out[2 * ((size_t)j * g.nx + i + plane * (size_t)k) + comp], w);
-        }
-      }
-    }
+// the sources of the plain spread (k_dp_spread_simple): the charge, and its image in each wall it is near; one complex grid, the real
+// part the near-wall charges themselves, the imaginary part everything else
+template <class U> struct DppSource {
+  static constexpr int kSources = 3, kAmplitudes = 1;
+  U half, ratioTop, ratioBot;
+  UH_D DpSource<U, 1> get(int n, int, const typename VecOf<U>::T4 &r, int flags) const {
+    DpSource<U, 1> s{true, r.z, {-r.w}, {0}, {(n == 0 && (flags & dpp::kNear)) ? 0 : 1}};
+    if (n == 1) { s.on = (flags & dpp::kTop) != 0; s.zs = U(2) * half - r.z; s.amplitude[0] = r.w * ratioTop; }
+    if (n == 2) { s.on = (flags & dpp::kBottom) != 0; s.zs = U(-2) * half - r.z; s.amplitude[0] = r.w * ratioBot; }
+    s.on = s.on && s.amplitude[0] != U(0);  // (a wall without a jump has images of charge zero: three times the atomic adds for nothing)
+    return s;
   }
-}
+};
 
 // ---- (2)-(5) both solves, both solutions at the walls, the mismatch ------------------------------------------------------------------
-template <class T> struct DppRow {
-  T *p;
-  size_t stride;
-  __device__ T &operator[](int i) const { return p[(size_t)i * stride]; }
-};
 // the Chebyshev coefficients of the right-hand side of one wave number, separated from the packed spectrum on the fly
 template <class U> struct DppRhs {
   using T2 = typename VecOf<U>::T2;
@@ -237,13 +178,11 @@ template <class U> struct DppRhs {
   U scale;
   bool inside;
   __device__ T2 operator[](int n) const {
-    const T2 a = g[s + nsys * n], b = g[sm + nsys * n];
-    T2 f;
-    f.x = U(0.5) * (a.x + b.x);
-    f.y = U(0.5) * (a.y - b.y);
+    T2 f = dp_hermitian_part<U>(g, nsys, s, sm, n, 0);
     if (inside) {
-      f.x += U(0.5) * (a.y + b.y);
-      f.y -= U(0.5) * (a.x - b.x);
+      const T2 b = dp_hermitian_part<U>(g, nsys, s, sm, n, 1);
+      f.x += b.x;
+      f.y += b.y;
     }
     f.x *= scale;
     f.y *= scale;
@@ -255,8 +194,6 @@ template <class U> struct DppWalls {
   U epsTop, epsBottom, epsInside, H;
   int metTop, metBottom;
 };
-
-template <class U> UH_D typename VecOf<U>::T2 cmul(typename VecOf<U>::T2 a, U s) { a.x *= s; a.y *= s; return a; }
 
 template <class U>
 __global__ __launch_bounds__(64) void k_dpp_solve(uammd::BVP::device::Tables<U> t, const typename VecOf<U>::T2 *__restrict__ spectrum, int nx, int ny,
@@ -278,7 +215,7 @@ __global__ __launch_bounds__(64) void k_dpp_solve(uammd::BVP::device::Tables<U> 
   T2 wall[2][4];  // [outside, inside][phi top, phi bottom, Ez top, Ez bottom]
   for (int which = 0; which < 2; ++which) {
     T2 *cn = which ? cnIn : cnOut;
-    uammd::BVP::device::solveSystem(t, s, DppRhs<U>{spectrum, n, s, sm, invEps, which == 1}, zero, zero, DppRow<T2>{an + s, n}, DppRow<T2>{cn + s, n});
+    uammd::BVP::device::solveSystem(t, s, DppRhs<U>{spectrum, n, s, sm, invEps, which == 1}, zero, zero, Row<T2>{an + s, n}, Row<T2>{cn + s, n});
     // dphi/dz by the backward recurrence (BVPPoisson.cuh:38-56), summed into the series at the two wall angles as it goes
     T2 d2 = zero, d1 = zero, pT = zero, pB = zero, eT = zero, eB = zero;
     for (int m = nz - 1; m >= 0; --m) {
@@ -352,13 +289,6 @@ struct DppCorrection {
   double epsTop, epsBottom, epsInside, H, He, kmax;
   int metTop, metBottom;
 };
-struct cd2 { double x, y; };
-UH_D cd2 operator+(cd2 a, cd2 b) { return {a.x + b.x, a.y + b.y}; }
-UH_D cd2 operator-(cd2 a, cd2 b) { return {a.x - b.x, a.y - b.y}; }
-UH_D cd2 operator-(cd2 a) { return {-a.x, -a.y}; }
-UH_D cd2 operator*(cd2 a, double s) { return {a.x * s, a.y * s}; }
-UH_D cd2 operator*(double s, cd2 a) { return {a.x * s, a.y * s}; }
-UH_D cd2 operator/(cd2 a, double s) { return {a.x / s, a.y / s}; }
 
 template <class U>
 __global__ __launch_bounds__(256) void k_dpp_correction(const typename VecOf<U>::T2 *__restrict__ mismatch, const U *__restrict__ kmod,
@@ -454,72 +384,23 @@ __global__ __launch_bounds__(64) void k_dpp_assemble(const typename VecOf<U>::T2
   }
 }
 
-// ---- (7) gather: a wave per particle, lanes over the x-y footprint, a loop over the planes -------------------------------------------
-template <class U>
-__global__ __launch_bounds__(256) void k_dpp_gather(const typename VecOf<U>::T4 *__restrict__ rec, const int4 *__restrict__ cellrec, int N,
-                                                    ChebGrid<U> g, const typename VecOf<U>::T2 *__restrict__ exy,
-                                                    const typename VecOf<U>::T2 *__restrict__ ezphi, typename VecOf<U>::T4 *__restrict__ force,
-                                                    U *__restrict__ energy, typename VecOf<U>::T4 *__restrict__ field) {
-  using T2 = typename VecOf<U>::T2;
-  const int lane = threadIdx.x & 63;
-  const int a = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (a >= N) return;
-  const int4 c = cellrec[a];
-  if (c.z & dpp::kOutside) return;
-  const typename VecOf<U>::T4 r = rec[a];
-  const int s = g.support, cols = s * s;
-  constexpr int G = (dpp::kMaxSupport * dpp::kMaxSupport + 63) / 64;
-  U wxy[G];
-  size_t node[G];
-#pragma unroll
-  for (int q = 0; q < G; ++q) {
-    const int col = lane + 64 * q;
-    wxy[q] = U(0);
-    node[q] = 0;
-    if (col < cols) {
-      const int jj = col / s, ii = col - jj * s;
-      const int i = ChebGrid<U>::wrap(c.x + ii, g.nx), j = ChebGrid<U>::wrap(c.y + jj, g.ny);
-      wxy[q] = g.weight_x(r.x, i) * g.weight_y(r.y, j);
-      node[q] = (size_t)j * g.nx + i;
+// ---- (7) gather (k_dp_gather): force += q E, energy += q phi, field += (E, phi) ---------------------------------------------------------
+template <class U> struct DppSink {
+  using T4 = typename VecOf<U>::T4;
+  UH_D static void outside(int, int, T4 *, U *, T4 *) {}
+  UH_D static void write(int a, const T4 &r, const U *sum, T4 *force, U *energy, T4 *field) {
+    const U q = r.w;
+    typename VecOf<U>::T4 f = force[a];
+    f.x += q * sum[0]; f.y += q * sum[1]; f.z += q * sum[2];
+    force[a] = f;
+    energy[a] += q * sum[3];
+    if (field) {
+      typename VecOf<U>::T4 e = field[a];
+      e.x += sum[0]; e.y += sum[1]; e.z += sum[2]; e.w += sum[3];
+      field[a] = e;
     }
   }
-  int lo, hi;
-  g.plane_range(r.z, lo, hi);
-  lo = __builtin_amdgcn_readfirstlane(lo);
-  hi = __builtin_amdgcn_readfirstlane(hi);
-  const size_t plane = (size_t)g.nx * g.ny;
-  U ax = U(0), ay = U(0), az = U(0), aw = U(0);
-  for (int k = lo; k <= hi; ++k) {
-    const U wz = g.phi(r.z - g.zplane[k]) * g.qw[k];  // the quadrature weight folded in
-    if (wz == U(0)) continue;
-#pragma unroll
-    for (int q = 0; q < G; ++q) {
-      if (64 * q < cols) {  // (wave-uniform)
-        const T2 u = exy[node[q] + plane * (size_t)k], v = ezphi[node[q] + plane * (size_t)k];
-        const U w = wxy[q] * wz;
-        ax += w * u.x; ay += w * u.y; az += w * v.x; aw += w * v.y;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ax += __shfl_xor(ax, o, 64);
-    ay += __shfl_xor(ay, o, 64);
-    az += __shfl_xor(az, o, 64);
-    aw += __shfl_xor(aw, o, 64);
-  }
-  if (lane != 0) return;
-  const U q = r.w;
-  typename VecOf<U>::T4 f = force[a];
-  f.x += q * ax; f.y += q * ay; f.z += q * az;
-  force[a] = f;
-  energy[a] += q * aw;
-  if (field) {
-    typename VecOf<U>::T4 e = field[a];
-    e.x += ax; e.y += ay; e.z += az; e.w += aw;
-    field[a] = e;
-  }
-}
+};
 
 // ---- near field (NearField.cuh:149-230) ----------------------------------------------------------------------------------------------
 template <class U>
@@ -667,19 +548,6 @@ static int next_fft_size(int n) {  // nextFFTWiseSize3D (utils/Grid.cuh:140-215)
   }
 }
 
-static double clencurt(int i, int n) {  // misc/ChevyshevUtils.cuh:13-30
-  double v = 1;
-  if (n % 2 == 0) {
-    if (i == 0 || i == n) return 1.0 / (n * (double)n - 1.0);
-    for (int k = 1; k <= n / 2 - 1; k++) v -= 2 * std::cos(2 * k * M_PI * i / n) / (4.0 * k * k - 1);
-    v -= std::cos(M_PI * i) / (n * (double)n - 1.0);
-  } else {
-    if (i == 0 || i == n) return 1.0 / (n * (double)n);
-    for (int k = 1; k <= (n - 1) / 2; k++) v -= 2 * std::cos(2 * k * M_PI * i / n) / (4.0 * k * k - 1);
-  }
-  return 2.0 * v / n;
-}
-
 // Everything the constructor decides, on the host in double (no device call): 0, or -2 with the reference's message.
 static int configure(const uammd_dppoisson_parameters &p, bool doublePrecision, Host &o) {
   const double top = p.permitivity[0], bottom = p.permitivity[1], inside = p.permitivity[2];
@@ -729,9 +597,9 @@ static int configure(const uammd_dppoisson_parameters &p, bool doublePrecision, 
   }
   o.h = p.Lxy[0] / o.cells[0];
   o.hy = p.Lxy[1] / o.cells[1];
-  if (p.support < 1 || p.support > kMaxSupport || p.support > std::min(o.cells[0], o.cells[1])) {
+  if (p.support < 1 || p.support > dp::kMaxSupport || p.support > std::min(o.cells[0], o.cells[1])) {
     set_last_error("uammd_dppoisson_create: support = %d; the window takes 1 to %d nodes per axis and must fit the %d x %d plane", p.support,
-                   kMaxSupport, o.cells[0], o.cells[1]);
+                   dp::kMaxSupport, o.cells[0], o.cells[1]);
     return -2;
   }
   {  // computeCutOffDistance (NearField.cuh:63-77)
@@ -773,25 +641,12 @@ struct DPPoisson {
   std::vector<std::complex<double>> hostSurf[2];
   CellList cl;
   bool ran = false;
-  // option time_stages: device events between the stage launches of a run (uammd_dppoisson_stage_times)
-  bool timeStages = false;
-  hipEvent_t stageEvent[dpp::kStages + 1] = {};
-  int stageMarks = 0;
-  hipStream_t stageStream = nullptr;
+  StageTimer<dpp::kStages> timer;  // option time_stages (uammd_dppoisson_stage_times)
   ~DPPoisson() {
-    for (hipEvent_t e : stageEvent)
-      if (e) (void)hipEventDestroy(e);
     if (fct) uammd_fct_destroy(fct);
     if (bvp) uammd_bvp_destroy(bvp);
   }
 };
-
-template <class U> static int upload(DeviceBuffer &b, const std::vector<double> &v) {
-  std::vector<U> tmp(v.begin(), v.end());
-  if (int e = b.reserve(std::max<size_t>(tmp.size(), 1) * sizeof(U))) return e;
-  if (!tmp.empty()) UH_CHECK(hipMemcpy(b.ptr, tmp.data(), tmp.size() * sizeof(U), hipMemcpyHostToDevice));
-  return 0;
-}
 
 template <class U> static int dpp_upload_surface(DPPoisson *h) {
   for (int wch = 0; wch < 2; ++wch) {
@@ -806,7 +661,7 @@ template <class U> static ChebGrid<U> dpp_grid(const DPPoisson *h) {
   ChebGrid<U> g;
   g.nx = h->cfg.cells[0]; g.ny = h->cfg.cells[1]; g.nz = h->cfg.cells[2];
   g.support = h->par.support;
-  g.Lx = (U)h->par.Lxy[0]; g.Ly = (U)h->par.Lxy[1]; g.Htot = (U)h->cfg.Htot;
+  g.Lx = (U)h->par.Lxy[0]; g.Ly = (U)h->par.Lxy[1]; g.span = (U)h->cfg.Htot;
   g.hx = (U)h->cfg.h; g.hy = (U)h->cfg.hy;
   g.invhx = (U)(1.0 / h->cfg.h); g.invhy = (U)(1.0 / h->cfg.hy);
   g.prefactor = (U)(1.0 / (h->cfg.gt * std::sqrt(2 * M_PI)));
@@ -825,25 +680,15 @@ template <class U> static int dpp_build(DPPoisson *h) {
   h->nsys = nsys;
   h->nz = nz;
   const double Hh = 0.5 * c.Htot;
-  std::vector<double> zp(nz), qw(nz), ct(nz), cb(nz), k(nsys), kx(nsys), ky(nsys), tfi(nsys), tsi(nsys), bfi(nsys), bsi(nsys);
+  std::vector<double> zp, qw, ct(nz), cb(nz), k(nsys), kx(nsys), ky(nsys), tfi(nsys), tsi(nsys), bfi(nsys), bsi(nsys);
+  dp::chebyshev_planes(nz, Hh, c.h, c.hy, zp, qw);
   for (int i = 0; i < nz; ++i) {
-    zp[i] = Hh * std::cos(M_PI * i / (nz - 1));
-    qw[i] = 0.5 * c.Htot * dpp::clencurt(i, nz - 1) * (c.h * c.hy);
     ct[i] = std::cos(i * c.thetaTop);
     cb[i] = std::cos(i * c.thetaBot);
   }
   for (int s = 0; s < nsys; ++s) {
-    const int i = s % nx, j = s / nx;
-    const double wx = 2 * M_PI / p.Lxy[0] * (i - nx * (i >= nx / 2 + 1)), wy = 2 * M_PI / p.Lxy[1] * (j - ny * (j >= ny / 2 + 1));
-    k[s] = std::sqrt(wx * wx + wy * wy);
-    // for an even size the unpaired Nyquist index carries no derivative along its axis; an odd size has no unpaired index
-    kx[s] = (nx % 2 == 0 && i == nx / 2) ? 0.0 : wx;
-    ky[s] = (ny % 2 == 0 && j == ny / 2) ? 0.0 : wy;
-    const bool nonzero = k[s] != 0;  // BoundaryConditions.cuh:13-33
-    tfi[s] = nonzero ? Hh : 0.0;
-    tsi[s] = nonzero ? Hh * Hh * k[s] : 1.0;
-    bfi[s] = nonzero ? Hh : 0.0;
-    bsi[s] = nonzero ? -Hh * Hh * k[s] : 1.0;
+    dp::wave_vector(s, nx, ny, p.Lxy[0], p.Lxy[1], kx[s], ky[s], k[s]);
+    dp::bvp_boundary_factors(k[s], Hh, tfi[s], tsi[s], bfi[s], bsi[s]);
   }
   int e = upload<U>(h->zplane, zp);
   if (!e) e = upload<U>(h->qw, qw);
@@ -903,16 +748,8 @@ static int dpp_run(DPPoisson *h, const void *d_pos, const void *d_charge, int N,
   for (int i = 0; i < 6; ++i) B[i] = (T2 *)h->field[i].ptr;
   const T4 *rec = (const T4 *)h->rec.ptr;
   const int4 *cellrec = (const int4 *)h->cellrec.ptr;
-  h->stageMarks = 0;
-  h->stageStream = st;
-  auto mark = [&]() -> int {  // one event after every stage; nothing is recorded, created or waited for unless time_stages is set
-    if (!h->timeStages) return 0;
-    hipEvent_t &e = h->stageEvent[h->stageMarks];
-    if (!e) UH_CHECK(hipEventCreate(&e));
-    UH_CHECK(hipEventRecord(e, st));
-    ++h->stageMarks;
-    return 0;
-  };
+  h->timer.reset();
+  auto mark = [&]() { return h->timer.mark(st); };
   if (int e = mark()) return e;
   // (1)
   UH_CHECK(hipMemsetAsync(h->counters.ptr, 0, 8 * sizeof(unsigned), st));
@@ -922,11 +759,10 @@ static int dpp_run(DPPoisson *h, const void *d_pos, const void *d_charge, int N,
   // (2, 3) one grid: real part the near-wall charges, imaginary part the rest and the images
   if (h->simpleSpread) {
     UH_CHECK(hipMemsetAsync(B[0], 0, sizeof(T2) * (size_t)nsys * nz, st));
-    hipLaunchKernelGGL((k_dpp_spread_simple<U>), dim3((N + 63) / 64), dim3(64), 0, st, rec, cellrec, N, g, half, ratioTop, ratioBot, (U *)B[0]);
+    hipLaunchKernelGGL((k_dp_spread_simple<U, ChebGrid<U>, DppSource<U>>), dim3((N + 63) / 64), dim3(64), 0, st, rec, cellrec, N, g,
+                       DppSource<U>{half, ratioTop, ratioBot}, (U *)B[0], (U *)nullptr);
   } else {
-    constexpr int T = dpp::kTile;
-    const dim3 grid(((g.nx + T - 1) / T) * ((g.ny + T - 1) / T), (nz + T - 1) / T);
-    hipLaunchKernelGGL((k_dpp_spread_owner<U>), grid, dim3(64), 0, st, rec, cellrec, N, g, half, ratioTop, ratioBot, B[0]);
+    hipLaunchKernelGGL((k_dpp_spread_owner<U>), dp_owner_grid(g.nx, g.ny, nz), dim3(64), 0, st, rec, cellrec, N, g, half, ratioTop, ratioBot, B[0]);
   }
   UH_CHECK(hipGetLastError());
   if (int e = mark()) return e;
@@ -934,13 +770,7 @@ static int dpp_run(DPPoisson *h, const void *d_pos, const void *d_charge, int N,
     if (int e = h->stageGrid.reserve(sizeof(T2) * (size_t)nsys * nz)) return e;
     UH_CHECK(hipMemcpyAsync(h->stageGrid.ptr, B[0], sizeof(T2) * (size_t)nsys * nz, hipMemcpyDeviceToDevice, st));
   }
-  auto fctRun = [&](bool planes, const T2 *in, T2 *out, int dir) -> int {
-    if (sizeof(U) == sizeof(double))
-      return planes ? uammd_fct_fourier_chebyshev_f64(h->fct, (const double *)in, (double *)out, dir, st)
-                    : uammd_fct_chebyshev_f64(h->fct, (const double *)in, (double *)out, dir, st);
-    return planes ? uammd_fct_fourier_chebyshev(h->fct, (const float *)in, (float *)out, dir, st)
-                  : uammd_fct_chebyshev(h->fct, (const float *)in, (float *)out, dir, st);
-  };
+  auto fctRun = [&](bool planes, const T2 *in, T2 *out, int dir) { return fct_run<U>(h->fct, planes, in, out, dir, st); };
   if (int e = fctRun(true, B[0], B[1], UAMMD_FCT_FORWARD)) return e;  // spectrum in B1
   if (int e = mark()) return e;
   // (2)-(5): an in B0 (the grid is spent), outside in B2, inside in B3
@@ -974,8 +804,8 @@ static int dpp_run(DPPoisson *h, const void *d_pos, const void *d_charge, int N,
   if (int e = fctRun(true, B[5], B[0], UAMMD_FCT_INVERSE)) return e;
   if (int e = mark()) return e;
   // (7)
-  hipLaunchKernelGGL((k_dpp_gather<U>), dim3((N + 3) / 4), dim3(256), 0, st, rec, cellrec, N, g, (const T2 *)B[2], (const T2 *)B[0], (T4 *)d_force,
-                     (U *)d_energy, (T4 *)d_field);
+  hipLaunchKernelGGL((k_dp_gather<U, ChebGrid<U>, 4, DppSink<U>, T4, U, T4>), dim3((N + 3) / 4), dim3(256), 0, st, rec, cellrec, N, g,
+                     (const T2 *)B[2], (const T2 *)B[0], (T4 *)d_force, (U *)d_energy, (T4 *)d_field);
   UH_CHECK(hipGetLastError());
   if (int e = mark()) return e;
   h->ran = true;
@@ -1005,10 +835,7 @@ static int dpp_entry(uammd_dppoisson *h_, bool wantDouble, const void *pos, cons
   DPPoisson *h = reinterpret_cast<DPPoisson *>(h_);
   if (!h) { set_last_error("%s: null handle", who); return -1; }
   if (virial) { set_last_error("[Poisson] not implemented (%s: the virial)", who); return -3; }
-  if (h->doublePrecision != wantDouble) {
-    set_last_error("%s: the handle was created for %s precision", who, h->doublePrecision ? "double" : "single");
-    return -1;
-  }
+  if (int e = dp_check_precision(h->doublePrecision, wantDouble, who)) return e;
   if (N < 0) { set_last_error("%s: numberParticles = %d", who, N); return -1; }
   if (N == 0) return 0;
   if (!pos || !charge || !force || !energy || (needField && !field)) { set_last_error("%s: null argument", who); return -1; }
@@ -1057,7 +884,7 @@ int uammd_dppoisson_set_option(uammd_dppoisson *h_, const char *name, int value)
   if (n == "simple_spread") { h->simpleSpread = value != 0; return 0; }
   if (n == "keep_stages") { h->keepStages = value != 0; return 0; }
   if (n == "skip_near_field") { h->skipNear = value != 0; return 0; }
-  if (n == "time_stages") { h->timeStages = value != 0; h->stageMarks = 0; return 0; }
+  if (n == "time_stages") { h->timer.enable(value != 0); return 0; }
   set_last_error("uammd_dppoisson_set_option: unknown option %s", name);
   return -1;
 }
@@ -1197,17 +1024,7 @@ int uammd_dppoisson_get_stage(uammd_dppoisson *h_, const char *name, void *d_out
 int uammd_dppoisson_stage_times(uammd_dppoisson *h_, double *ms) {
   DPPoisson *h = reinterpret_cast<DPPoisson *>(h_);
   if (!h || !ms) { set_last_error("uammd_dppoisson_stage_times: null argument"); return -1; }
-  if (!h->timeStages || h->stageMarks < 2) { set_last_error("uammd_dppoisson_stage_times: set option time_stages before the call"); return -1; }
-  UH_CHECK(hipEventSynchronize(h->stageEvent[h->stageMarks - 1]));
-  for (int i = 0; i < dpp::kStages; ++i) {
-    ms[i] = 0;
-    if (i + 1 < h->stageMarks) {
-      float t = 0;
-      UH_CHECK(hipEventElapsedTime(&t, h->stageEvent[i], h->stageEvent[i + 1]));
-      ms[i] = t;
-    }
-  }
-  return 0;
+  return h->timer.times(ms, "uammd_dppoisson_stage_times");
 }
 
 }  // extern "C"

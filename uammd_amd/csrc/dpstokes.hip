@@ -29,8 +29,7 @@
 //  * The correction is evaluated in double in either build, as section 17 does; every exponent is <= 0.
 // A particle with |z| > H/2 (or a non-finite coordinate) is never spread or gathered and receives zero; it is counted.  The reference has
 // no such guard.
-#include "celllist.hpp"
-#include "cheb_grid.hpp"
+#include "dp_slab.hpp"
 #include "dpstokes_host.hpp"
 #include "saru.hpp"
 #include "../../include/uammd/device/BVP.hip.hpp"
@@ -44,14 +43,8 @@
 namespace uammd_hip {
 
 namespace dps {
-template <class U> struct Vec;
-template <> struct Vec<float> { using T2 = float2; };
-template <> struct Vec<double> { using T2 = double2; };
-
-constexpr int kOutside = 8;
-constexpr int kMaxSupport = 16;  // the gather keeps ceil(support^2 / 64) <= 4 columns per lane (dpp::kMaxSupport)
-constexpr int kStages = 13;      // uammd_dpstokes_stage_times
-constexpr int kTile = 8;         // the owner spread's block: kTile x kTile nodes x kTile planes per wave
+constexpr int kOutside = dp::kOutside;
+constexpr int kStages = 13;  // uammd_dpstokes_stage_times
 constexpr int kFields = 14;
 
 struct Host {  // everything create() works out before it touches the device
@@ -59,10 +52,6 @@ struct Host {  // everything create() works out before it touches the device
   double hx = 0, hy = 0, az = 0, rmax = 0, beta[3] = {0, 0, 0}, invnorm[3] = {0, 0, 0};
   double wmax = 0;  // an upper bound of a window's weight at a node: phi_x(0) phi_y(0) phi_z(0), and a hair
 };
-
-template <class U> UH_D U bcast(U v, int lane) { return __shfl(v, lane, 64); }
-
-template <class U> struct rec4 { U x, y, z, w; };
 
 UH_D unsigned long long bits(float v) { return (unsigned long long)__float_as_uint(v); }
 UH_D unsigned long long bits(double v) { return (unsigned long long)__double_as_longlong(v); }
@@ -77,7 +66,7 @@ UH_D double fmax_(double a, double b) { return fmax(a, b); }
 // ---- (1) classification: the flag, the folded coordinates, the window's first nodes ---------------------------------------------------
 template <class U>
 __global__ __launch_bounds__(256) void k_dps_classify(const U *__restrict__ pos, int ps, const U *__restrict__ force, int fs, int N,
-                                                      ChebGridBM<U> g, U half, dps::rec4<U> *__restrict__ rec, int4 *__restrict__ cellrec,
+                                                      ChebGridBM<U> g, U half, typename VecOf<U>::T4 *__restrict__ rec, int4 *__restrict__ cellrec,
                                                       unsigned *__restrict__ counters) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool active = i < N;
@@ -85,19 +74,16 @@ __global__ __launch_bounds__(256) void k_dps_classify(const U *__restrict__ pos,
   U fmax = U(0);
   if (active) {
     const U px = pos[(size_t)i * ps], py = pos[(size_t)i * ps + 1], pz = pos[(size_t)i * ps + 2];
-    const bool finite = (px - px == U(0)) && (py - py == U(0)) && (pz - pz == U(0));
-    dps::rec4<U> r{U(0), U(0), U(0), U(0)};
+    typename VecOf<U>::T4 r;
+    r.x = r.y = r.z = r.w = U(0);
     int4 c = make_int4(0, 0, 0, 0);
-    if (!finite || !(abs_(pz) <= half)) {
+    // (read before the window is placed, so that the loads are in flight meanwhile; a particle outside the slab does not use it)
+    const U largest = fmax_(fmax_(abs_(force[(size_t)i * fs]), abs_(force[(size_t)i * fs + 1])), abs_(force[(size_t)i * fs + 2]));
+    if (!dp_place(g, px, py, pz, half, r, c)) {
       outside = true;
       c.z = dps::kOutside;
     } else {
-      r.x = ChebGrid<U>::fold(px, g.Lx);
-      r.y = ChebGrid<U>::fold(py, g.Ly);
-      r.z = pz;
-      c.x = g.leftmost_x(r.x);
-      c.y = g.leftmost_y(r.y);
-      fmax = fmax_(fmax_(abs_(force[(size_t)i * fs]), abs_(force[(size_t)i * fs + 1])), abs_(force[(size_t)i * fs + 2]));
+      fmax = largest;
     }
     rec[i] = r;
     cellrec[i] = c;
@@ -130,151 +116,88 @@ template <class U> UH_D double dps_spread_scale(const unsigned *counters, U wmax
   return ldexp(1.0, shift);
 }
 
-// ---- (2) the spread, owner-computes ----------------------------------------------------------------------------------------------------
-UH_D bool dps_ring_overlap(int first, int width, int tile0, int n) {  // [first, first + width) against [tile0, tile0 + kTile) mod n
-  int d = tile0 - first;
-  d = d < 0 ? d + n : (d >= n ? d - n : d);
-  return d < width || n - d < dps::kTile;
-}
-
+// ---- (2) the spread, owner-computes (the tile and the scan: DpTile) ----------------------------------------------------------------------
 template <class U>
-__global__ __launch_bounds__(64) void k_dps_spread_owner(const dps::rec4<U> *__restrict__ rec, const int4 *__restrict__ cellrec,
+__global__ __launch_bounds__(64) void k_dps_spread_owner(const typename VecOf<U>::T4 *__restrict__ rec, const int4 *__restrict__ cellrec,
                                                          const U *__restrict__ force, int fs, int N, ChebGridBM<U> g,
                                                          const unsigned *__restrict__ counters, U wmax,
-                                                         typename dps::Vec<U>::T2 *__restrict__ outXY, typename dps::Vec<U>::T2 *__restrict__ outZ) {
-  constexpr int T = dps::kTile;
+                                                         typename VecOf<U>::T2 *__restrict__ outXY, typename VecOf<U>::T2 *__restrict__ outZ) {
+  constexpr int T = dp::kTile;
   const double scale = dps_spread_scale<U>(counters, wmax);
-  const int lane = threadIdx.x;
-  const int tilesX = (g.nx + T - 1) / T;
-  const int tx0 = (int)(blockIdx.x % tilesX) * T, ty0 = (int)(blockIdx.x / tilesX) * T, p0 = (int)blockIdx.y * T;
-  const int ni = tx0 + (lane & (T - 1)), nj = ty0 + (lane >> 3);
-  const bool nodeOK = ni < g.nx && nj < g.ny;
-  const int last = g.nz - 1;
-  const U zTop = g.zplane[p0], zBottom = g.zplane[min(p0 + T - 1, last)];  // the block's planes span [zBottom, zTop]
-  const U zMine = g.zplane[min(p0 + (lane & (T - 1)), last)];               // lanes 0-7 evaluate the z weight of plane p0 + lane
-  const bool planeMine = lane < T && p0 + lane <= last;
+  const DpTile<U, ChebGridBM<U>> tile(g);
+  const bool planeMine = tile.lane < T && tile.planeOK;  // lanes 0-7 evaluate the z weight of plane p0 + lane
   long long accX[T], accY[T], accZ[T];
 #pragma unroll
   for (int p = 0; p < T; ++p) accX[p] = accY[p] = accZ[p] = 0;
-  for (int base = 0; base < N; base += 64) {
-    const int a = base + lane;
-    dps::rec4<U> r{U(0), U(0), U(0), U(0)};
-    U fx = U(0), fy = U(0), fz = U(0);
-    int4 c = make_int4(0, 0, dps::kOutside, 0);
-    bool hit = false;
-    if (a < N) {
-      c = cellrec[a];
-      r = rec[a];
-      if (!(c.z & dps::kOutside)) {
-        hit = r.z - g.reachz <= zTop && r.z + g.reachz >= zBottom && dps_ring_overlap(c.x, g.support, tx0, g.nx) &&
-              dps_ring_overlap(c.y, g.support, ty0, g.ny);
+  typename VecOf<U>::T4 r;
+  U fx, fy, fz;
+  int4 c;
+  tile.scan(
+      N,
+      [&](int a) {
+        r.x = r.y = r.z = r.w = U(0);
+        fx = fy = fz = U(0);
+        c = make_int4(0, 0, dps::kOutside, 0);
+        if (a >= N) return false;
+        c = cellrec[a];
+        r = rec[a];
+        if (c.z & dps::kOutside) return false;
+        const bool hit = tile.touches_z(g, r.z) && tile.touches_xy(g, c);
         if (hit) { fx = force[(size_t)a * fs]; fy = force[(size_t)a * fs + 1]; fz = force[(size_t)a * fs + 2]; }
-      }
-    }
-    unsigned long long m = __ballot(hit);
-    while (m) {  // the hits of this batch, in index order (wave-uniform)
-      const int l = __builtin_ctzll(m);
-      m &= m - 1;
-      const U px = dps::bcast(r.x, l), py = dps::bcast(r.y, l), pz = dps::bcast(r.z, l);
-      const U qx = dps::bcast(fx, l), qy = dps::bcast(fy, l), qz = dps::bcast(fz, l);
-      const int x0 = __shfl(c.x, l, 64), y0 = __shfl(c.y, l, 64);
-      const int ii = ChebGrid<U>::wrap(ni - x0, g.nx), jj = ChebGrid<U>::wrap(nj - y0, g.ny);
-      U wxy = U(0);
-      if (nodeOK && ii < g.support && jj < g.support) wxy = g.weight_x(px, ni) * g.weight_y(py, nj);
-      const U wl = planeMine ? g.weight_z(pz, zMine) : U(0);
+        return hit;
+      },
+      [&](int l) {
+        const U px = bcast(r.x, l), py = bcast(r.y, l), pz = bcast(r.z, l);
+        const U qx = bcast(fx, l), qy = bcast(fy, l), qz = bcast(fz, l);
+        const U wxy = tile.wxy(g, px, py, __shfl(c.x, l, 64), __shfl(c.y, l, 64));
+        const U wl = planeMine ? g.weight_z(pz, tile.zMine) : U(0);
 #pragma unroll
-      for (int p = 0; p < T; ++p) {
-        const U w = wxy * dps::bcast(wl, p);
-        accX[p] += (long long)((double)(w * qx) * scale);
-        accY[p] += (long long)((double)(w * qy) * scale);
-        accZ[p] += (long long)((double)(w * qz) * scale);
-      }
-    }
-  }
-  if (!nodeOK) return;
-  const size_t plane = (size_t)g.nx * g.ny, node = (size_t)nj * g.nx + ni;
+        for (int p = 0; p < T; ++p) {
+          const U w = wxy * bcast(wl, p);
+          accX[p] += (long long)((double)(w * qx) * scale);
+          accY[p] += (long long)((double)(w * qy) * scale);
+          accZ[p] += (long long)((double)(w * qz) * scale);
+        }
+      });
+  if (!tile.nodeOK) return;
   const double back = scale == 0.0 ? 0.0 : 1.0 / scale;  // (a power of two, or NaN when a force is not finite)
 #pragma unroll
   for (int p = 0; p < T; ++p)
-    if (p0 + p <= last) {
-      typename dps::Vec<U>::T2 v;
+    if (tile.has_plane(p)) {
+      typename VecOf<U>::T2 v;
       v.x = (U)((double)accX[p] * back); v.y = (U)((double)accY[p] * back);
-      outXY[node + plane * (size_t)(p0 + p)] = v;
+      outXY[tile.at(g, p)] = v;
       v.x = (U)((double)accZ[p] * back); v.y = U(0);
-      outZ[node + plane * (size_t)(p0 + p)] = v;
+      outZ[tile.at(g, p)] = v;
     }
 }
 
-// the cross-check: a lane per particle, atomic adds into zeroed grids
-template <class U>
-__global__ __launch_bounds__(64) void k_dps_spread_simple(const dps::rec4<U> *__restrict__ rec, const int4 *__restrict__ cellrec,
-                                                          const U *__restrict__ force, int fs, int N, ChebGridBM<U> g, U *__restrict__ outXY,
-                                                          U *__restrict__ outZ) {
-  const int a = blockIdx.x * 64 + threadIdx.x;
-  if (a >= N) return;
-  const int4 c = cellrec[a];
-  if (c.z & dps::kOutside) return;
-  const dps::rec4<U> r = rec[a];
-  const U fx = force[(size_t)a * fs], fy = force[(size_t)a * fs + 1], fz = force[(size_t)a * fs + 2];
-  const size_t plane = (size_t)g.nx * g.ny;
-  int lo, hi;
-  g.plane_range(r.z, lo, hi);
-  for (int k = lo; k <= hi; ++k) {
-    const U wz = g.weight_z(r.z, g.zplane[k]);
-    if (wz == U(0)) continue;
-    for (int jj = 0; jj < g.support; ++jj) {
-      const int j = ChebGrid<U>::wrap(c.y + jj, g.ny);
-      const U wy = g.weight_y(r.y, j);
-      for (int ii = 0; ii < g.support; ++ii) {
-        const int i = ChebGrid<U>::wrap(c.x + ii, g.nx);
-        const U w = (g.weight_x(r.x, i) * wy) * wz;
-        if (w == U(0)) continue;
-        const size_t at = 2 * ((size_t)j * g.nx + i + plane * (size_t)k);
-        unsafeAtomicAdd(&outXY[at], w * fx);
-        unsafeAtomicAdd(&outXY[at + 1], w * fy);
-        unsafeAtomicAdd(&outZ[at], w * fz);
-      }
-    }
+// the one source of the plain spread (k_dp_spread_simple): the force, (fx, fy) into the first grid and fz into the real part of the second
+template <class U> struct DpsSource {
+  static constexpr int kSources = 1, kAmplitudes = 3;
+  const U *force;
+  int fs;
+  UH_D DpSource<U, 3> get(int, int a, const typename VecOf<U>::T4 &r, int) const {
+    return {true, r.z, {force[(size_t)a * fs], force[(size_t)a * fs + 1], force[(size_t)a * fs + 2]}, {0, 0, 1}, {0, 1, 0}};
   }
-}
-
-// ---- (4, 5) the solves -----------------------------------------------------------------------------------------------------------------
-template <class T> struct DpsRow {
-  T *p;
-  size_t stride;
-  __device__ T &operator[](int i) const { return p[(size_t)i * stride]; }
 };
 
+// ---- (4, 5) the solves -----------------------------------------------------------------------------------------------------------------
 // Chebyshev coefficient n of component c (0, 1: the two real fields packed in one spectrum; 2: the real field of the other spectrum) of
-// wave number s, sm its mirror: A(k) = (G(k) + conj G(-k)) / 2, B(k) = (G(k) - conj G(-k)) / (2 i)
-template <class U> UH_D typename dps::Vec<U>::T2 dps_component(const typename dps::Vec<U>::T2 *xy, const typename dps::Vec<U>::T2 *z, size_t nsys,
-                                                               int s, int sm, int n, int c) {
-  const typename dps::Vec<U>::T2 *g = c == 2 ? z : xy;
-  const typename dps::Vec<U>::T2 a = g[s + nsys * n], b = g[sm + nsys * n];
-  typename dps::Vec<U>::T2 f;
-  if (c == 1) {
-    f.x = U(0.5) * (a.y + b.y);
-    f.y = -(U(0.5) * (a.x - b.x));
-  } else {
-    f.x = U(0.5) * (a.x + b.x);
-    f.y = U(0.5) * (a.y - b.y);
-  }
-  return f;
-}
-
-UH_D int dps_mirror(int s, int nx, int ny) {
-  const int i = s % nx, j = s / nx;
-  return (i ? nx - i : 0) + nx * (j ? ny - j : 0);
+// wave number s, sm its mirror
+template <class U> UH_D typename VecOf<U>::T2 dps_component(const typename VecOf<U>::T2 *xy, const typename VecOf<U>::T2 *z, size_t nsys,
+                                                            int s, int sm, int n, int c) {
+  return dp_hermitian_part<U>(c == 2 ? z : xy, nsys, s, sm, n, c == 1 ? 1 : 0);
 }
 
 // the pressure: y'' - k^2 y = i k . f + d fz / dz, alpha = beta = 0 (BVPStokes.cuh:54-76, :239-245)
 template <class U>
-__global__ __launch_bounds__(64) void k_dps_pressure(uammd::BVP::device::Tables<U> t, const typename dps::Vec<U>::T2 *__restrict__ specXY,
-                                                     const typename dps::Vec<U>::T2 *__restrict__ specZ, int nx, int ny, U invHalfHeight,
+__global__ __launch_bounds__(64) void k_dps_pressure(uammd::BVP::device::Tables<U> t, const typename VecOf<U>::T2 *__restrict__ specXY,
+                                                     const typename VecOf<U>::T2 *__restrict__ specZ, int nx, int ny, U invHalfHeight,
                                                      const U *__restrict__ kxPaired, const U *__restrict__ kyPaired,
-                                                     typename dps::Vec<U>::T2 *__restrict__ rhs, typename dps::Vec<U>::T2 *__restrict__ an,
-                                                     typename dps::Vec<U>::T2 *__restrict__ pressure) {
-  using T2 = typename dps::Vec<U>::T2;
+                                                     typename VecOf<U>::T2 *__restrict__ rhs, typename VecOf<U>::T2 *__restrict__ an,
+                                                     typename VecOf<U>::T2 *__restrict__ pressure) {
+  using T2 = typename VecOf<U>::T2;
   const int s = blockIdx.x * 64 + threadIdx.x;
   const int nsys = nx * ny;
   if (s >= nsys) return;
@@ -286,7 +209,7 @@ __global__ __launch_bounds__(64) void k_dps_pressure(uammd::BVP::device::Tables<
     for (int m = 0; m < nz; ++m) pressure[n * m] = zero;
     return;
   }
-  const int sm = dps_mirror(s, nx, ny);
+  const int sm = dps::mirror(s, nx, ny);
   const U kx = kxPaired[s], ky = kyPaired[s];
   T2 d2 = zero, d1 = zero;
   for (int m = nz - 1; m >= 0; --m) {
@@ -305,20 +228,20 @@ __global__ __launch_bounds__(64) void k_dps_pressure(uammd::BVP::device::Tables<
     r.y = (kx * fx.x + ky * fy.x) + d.y;
     rhs[s + n * m] = r;
   }
-  uammd::BVP::device::solveSystem(t, s, DpsRow<T2>{rhs + s, n}, zero, zero, DpsRow<T2>{an + s, n}, DpsRow<T2>{pressure + s, n});
+  uammd::BVP::device::solveSystem(t, s, Row<T2>{rhs + s, n}, zero, zero, Row<T2>{an + s, n}, Row<T2>{pressure + s, n});
 }
 
 // the three velocities, a lane per (wave number, component): right-hand sides and boundary values of BVPStokes.cuh:78-184, then the
 // solution at the two walls (sums and alternating sums of its coefficients)
 template <class U>
-__global__ __launch_bounds__(64) void k_dps_velocity(uammd::BVP::device::Tables<U> t, const typename dps::Vec<U>::T2 *__restrict__ specXY,
-                                                     const typename dps::Vec<U>::T2 *__restrict__ specZ,
-                                                     const typename dps::Vec<U>::T2 *__restrict__ pressure, int nx, int ny, U invHalfHeight,
+__global__ __launch_bounds__(64) void k_dps_velocity(uammd::BVP::device::Tables<U> t, const typename VecOf<U>::T2 *__restrict__ specXY,
+                                                     const typename VecOf<U>::T2 *__restrict__ specZ,
+                                                     const typename VecOf<U>::T2 *__restrict__ pressure, int nx, int ny, U invHalfHeight,
                                                      U viscosity, const U *__restrict__ kmod, const U *__restrict__ kxPaired,
-                                                     const U *__restrict__ kyPaired, typename dps::Vec<U>::T2 *__restrict__ rhs,
-                                                     typename dps::Vec<U>::T2 *__restrict__ an, typename dps::Vec<U>::T2 *__restrict__ vel,
-                                                     typename dps::Vec<U>::T2 *__restrict__ wall) {
-  using T2 = typename dps::Vec<U>::T2;
+                                                     const U *__restrict__ kyPaired, typename VecOf<U>::T2 *__restrict__ rhs,
+                                                     typename VecOf<U>::T2 *__restrict__ an, typename VecOf<U>::T2 *__restrict__ vel,
+                                                     typename VecOf<U>::T2 *__restrict__ wall) {
+  using T2 = typename VecOf<U>::T2;
   const int id = blockIdx.x * 64 + threadIdx.x;
   const int nsys = nx * ny;
   if (id >= 3 * nsys) return;
@@ -334,7 +257,7 @@ __global__ __launch_bounds__(64) void k_dps_velocity(uammd::BVP::device::Tables<
     wall[(size_t)2 * id + 1] = zero;
     return;
   }
-  const int sm = dps_mirror(s, nx, ny);
+  const int sm = dps::mirror(s, nx, ny);
   const U invmu = U(1.0) / viscosity;
   const T2 *p = pressure + s;
   T2 pH = zero, pmH = zero;
@@ -379,7 +302,7 @@ __global__ __launch_bounds__(64) void k_dps_velocity(uammd::BVP::device::Tables<
     alpha.x = fac * pH.x; alpha.y = fac * pH.y;
     beta.x = fac * pmH.x; beta.y = fac * pmH.y;
   }
-  uammd::BVP::device::solveSystem(t, s, DpsRow<T2>{r, n}, alpha, beta, DpsRow<T2>{a, n}, DpsRow<T2>{out, n});
+  uammd::BVP::device::solveSystem(t, s, Row<T2>{r, n}, alpha, beta, Row<T2>{a, n}, Row<T2>{out, n});
   T2 top = zero, bot = zero;
   for (int m = 0; m < nz; ++m) {
     const T2 v = out[n * m];
@@ -392,20 +315,10 @@ __global__ __launch_bounds__(64) void k_dps_velocity(uammd::BVP::device::Tables<
 }
 
 // ---- (6) the wall correction (Correction.cuh), in double ---------------------------------------------------------------------------------
-struct cd2 { double x, y; };
-UH_D cd2 operator+(cd2 a, cd2 b) { return {a.x + b.x, a.y + b.y}; }
-UH_D cd2 operator-(cd2 a, cd2 b) { return {a.x - b.x, a.y - b.y}; }
-UH_D cd2 operator-(cd2 a) { return {-a.x, -a.y}; }
-UH_D cd2 operator*(cd2 a, double s) { return {a.x * s, a.y * s}; }
-UH_D cd2 operator*(double s, cd2 a) { return {a.x * s, a.y * s}; }
-UH_D cd2 cmul(cd2 a, cd2 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-UH_D cd2 times_i(cd2 a) { return {-a.y, a.x}; }
-UH_D cd2 times_minus_i(cd2 a) { return {a.y, -a.x}; }
-
 // the constants of a wave number, 8 complex at c nsys + s: slit C = A^-1 b (fillRightHandSide, Correction.cuh:286-324); bottom keeps
 // (u0, v0, w0) = minus the solution at the bottom wall in the first three
 template <class U>
-__global__ __launch_bounds__(64) void k_dps_constants(const typename dps::Vec<U>::T2 *__restrict__ wall, const double2 *__restrict__ invA,
+__global__ __launch_bounds__(64) void k_dps_constants(const typename VecOf<U>::T2 *__restrict__ wall, const double2 *__restrict__ invA,
                                                       const double *__restrict__ kxPaired, const double *__restrict__ kyPaired, int nsys, int mode,
                                                       double2 *__restrict__ constants) {
   const int s = blockIdx.x * 64 + threadIdx.x;
@@ -413,7 +326,7 @@ __global__ __launch_bounds__(64) void k_dps_constants(const typename dps::Vec<U>
   const size_t n = (size_t)nsys;
   cd2 top[3], bot[3];
   for (int c = 0; c < 3; ++c) {
-    const typename dps::Vec<U>::T2 t = wall[2 * (c * n + s)], b = wall[2 * (c * n + s) + 1];
+    const typename VecOf<U>::T2 t = wall[2 * (c * n + s)], b = wall[2 * (c * n + s) + 1];
     top[c] = cd2{-(double)t.x, -(double)t.y};
     bot[c] = cd2{-(double)b.x, -(double)b.y};
   }
@@ -447,7 +360,7 @@ template <class U>
 __global__ __launch_bounds__(256) void k_dps_correction(const double2 *__restrict__ constants, const double *__restrict__ kmod,
                                                         const double *__restrict__ kxPaired, const double *__restrict__ kyPaired,
                                                         const double *__restrict__ zplane, int nsys, int nz, int mode, double H, double viscosity,
-                                                        typename dps::Vec<U>::T2 *__restrict__ out) {
+                                                        typename VecOf<U>::T2 *__restrict__ out) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)nsys * nz) return;
   const int s = (int)(idx % (size_t)nsys), plane = (int)(idx / (size_t)nsys);
@@ -475,7 +388,7 @@ __global__ __launch_bounds__(256) void k_dps_correction(const double2 *__restric
       w = (k * w0 + times_minus_i(S)) * (z * ekz) + w0 * ekz;
     }
   }
-  typename dps::Vec<U>::T2 o;
+  typename VecOf<U>::T2 o;
   o.x = (U)u.x; o.y = (U)u.y; out[idx] = o;
   o.x = (U)v.x; o.y = (U)v.y; out[field + idx] = o;
   o.x = (U)w.x; o.y = (U)w.y; out[2 * field + idx] = o;
@@ -484,9 +397,9 @@ __global__ __launch_bounds__(256) void k_dps_correction(const double2 *__restric
 
 // the zero mode: mu u'' = -f for x (lane 0) and y (lane 1) with the mode's boundary rows, -D (c0; d0) = C f (Correction.cuh:70-126)
 template <class U>
-__global__ __launch_bounds__(64) void k_dps_zero_mode(uammd::BVP::device::Tables<U> t0, const typename dps::Vec<U>::T2 *__restrict__ specXY,
-                                                      size_t nsys, U viscosity, typename dps::Vec<U>::T2 *__restrict__ scratch) {
-  using T2 = typename dps::Vec<U>::T2;
+__global__ __launch_bounds__(64) void k_dps_zero_mode(uammd::BVP::device::Tables<U> t0, const typename VecOf<U>::T2 *__restrict__ specXY,
+                                                      size_t nsys, U viscosity, typename VecOf<U>::T2 *__restrict__ scratch) {
+  using T2 = typename VecOf<U>::T2;
   const int c = threadIdx.x;
   if (c >= 2) return;
   const int nz = t0.nz;
@@ -506,11 +419,11 @@ __global__ __launch_bounds__(64) void k_dps_zero_mode(uammd::BVP::device::Tables
 
 // ---- add the correction and the zero mode, keep the corrected coefficients, pack them as (u + i v), (w + i p) ---------------------------
 template <class U>
-__global__ __launch_bounds__(64) void k_dps_assemble(typename dps::Vec<U>::T2 *__restrict__ vel, typename dps::Vec<U>::T2 *__restrict__ pressure,
-                                                     const typename dps::Vec<U>::T2 *__restrict__ corr, const typename dps::Vec<U>::T2 *__restrict__ zeroMode,
-                                                     int nsys, int nz, int mode, typename dps::Vec<U>::T2 *__restrict__ uv,
-                                                     typename dps::Vec<U>::T2 *__restrict__ wp) {
-  using T2 = typename dps::Vec<U>::T2;
+__global__ __launch_bounds__(64) void k_dps_assemble(typename VecOf<U>::T2 *__restrict__ vel, typename VecOf<U>::T2 *__restrict__ pressure,
+                                                     const typename VecOf<U>::T2 *__restrict__ corr, const typename VecOf<U>::T2 *__restrict__ zeroMode,
+                                                     int nsys, int nz, int mode, typename VecOf<U>::T2 *__restrict__ uv,
+                                                     typename VecOf<U>::T2 *__restrict__ wp) {
+  using T2 = typename VecOf<U>::T2;
   const int s = blockIdx.x * 64 + threadIdx.x;
   if (s >= nsys) return;
   const size_t n = (size_t)nsys, field = n * nz;
@@ -541,66 +454,17 @@ __global__ __launch_bounds__(64) void k_dps_assemble(typename dps::Vec<U>::T2 *_
   }
 }
 
-// ---- (7) gather: a wave per particle, lanes over the x-y footprint, a loop over the planes ----------------------------------------------
-template <class U>
-__global__ __launch_bounds__(256) void k_dps_gather(const dps::rec4<U> *__restrict__ rec, const int4 *__restrict__ cellrec, int N, ChebGridBM<U> g,
-                                                    const typename dps::Vec<U>::T2 *__restrict__ uv, const typename dps::Vec<U>::T2 *__restrict__ wp,
-                                                    U *__restrict__ mf) {
-  using T2 = typename dps::Vec<U>::T2;
-  const int lane = threadIdx.x & 63;
-  const int a = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (a >= N) return;
-  const int4 c = cellrec[a];
-  if (c.z & dps::kOutside) {
+// ---- (7) gather (k_dp_gather): the three velocities; a particle outside the slab receives zero -------------------------------------------
+template <class U> struct DpsSink {
+  UH_D static void outside(int a, int lane, U *mf) {
     if (lane < 3) mf[(size_t)3 * a + lane] = U(0);
-    return;
   }
-  const dps::rec4<U> r = rec[a];
-  const int s = g.support, cols = s * s;
-  constexpr int G = (dps::kMaxSupport * dps::kMaxSupport + 63) / 64;
-  U wxy[G];
-  size_t node[G];
-#pragma unroll
-  for (int q = 0; q < G; ++q) {
-    const int col = lane + 64 * q;
-    wxy[q] = U(0);
-    node[q] = 0;
-    if (col < cols) {
-      const int jj = col / s, ii = col - jj * s;
-      const int i = ChebGrid<U>::wrap(c.x + ii, g.nx), j = ChebGrid<U>::wrap(c.y + jj, g.ny);
-      wxy[q] = g.weight_x(r.x, i) * g.weight_y(r.y, j);
-      node[q] = (size_t)j * g.nx + i;
-    }
+  UH_D static void write(int a, const typename VecOf<U>::T4 &, const U *sum, U *mf) {
+    mf[(size_t)3 * a] = sum[0];
+    mf[(size_t)3 * a + 1] = sum[1];
+    mf[(size_t)3 * a + 2] = sum[2];
   }
-  int lo, hi;
-  g.plane_range(r.z, lo, hi);
-  lo = __builtin_amdgcn_readfirstlane(lo);
-  hi = __builtin_amdgcn_readfirstlane(hi);
-  const size_t plane = (size_t)g.nx * g.ny;
-  U ax = U(0), ay = U(0), az = U(0);
-  for (int k = lo; k <= hi; ++k) {
-    const U wz = g.weight_z(r.z, g.zplane[k]) * g.qw[k];  // the quadrature weight folded in
-    if (wz == U(0)) continue;
-#pragma unroll
-    for (int q = 0; q < G; ++q) {
-      if (64 * q < cols) {  // (wave-uniform)
-        const T2 u = uv[node[q] + plane * (size_t)k], v = wp[node[q] + plane * (size_t)k];
-        const U w = wxy[q] * wz;
-        ax += w * u.x; ay += w * u.y; az += w * v.x;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ax += __shfl_xor(ax, o, 64);
-    ay += __shfl_xor(ay, o, 64);
-    az += __shfl_xor(az, o, 64);
-  }
-  if (lane != 0) return;
-  mf[(size_t)3 * a] = ax;
-  mf[(size_t)3 * a + 1] = ay;
-  mf[(size_t)3 * a + 2] = az;
-}
+};
 
 // ---- the integrator's kernels (DPStokesSlab.cuh:363-418) ----------------------------------------------------------------------------------
 template <class U> __global__ __launch_bounds__(256) void k_dps_noise(U *__restrict__ out, int N, uint s1, uint s2, float std) {
@@ -647,19 +511,6 @@ __global__ __launch_bounds__(256) void k_dps_update(U *__restrict__ pos, int ps,
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 namespace dps {
 
-static double clencurt(int i, int n) {  // misc/ChevyshevUtils.cuh:13-30
-  double v = 1;
-  if (n % 2 == 0) {
-    if (i == 0 || i == n) return 1.0 / (n * (double)n - 1.0);
-    for (int k = 1; k <= n / 2 - 1; k++) v -= 2 * std::cos(2 * k * M_PI * i / n) / (4.0 * k * k - 1);
-    v -= std::cos(M_PI * i) / (n * (double)n - 1.0);
-  } else {
-    if (i == 0 || i == n) return 1.0 / (n * (double)n);
-    for (int k = 1; k <= (n - 1) / 2; k++) v -= 2 * std::cos(2 * k * M_PI * i / n) / (4.0 * k * k - 1);
-  }
-  return 2.0 * v / n;
-}
-
 static double bm_norm(double alpha, double beta) {  // IBM_kernels.cuh:60-97: 2 Simpson(BM, 0, alpha) on 20000 intervals, compensated sum
   const int Nr = 20000;
   const double dx = alpha / Nr;
@@ -700,9 +551,9 @@ static int configure(const uammd_dpstokes_parameters &p, Host &o) {
     return -2;
   }
   o.support = (int)(p.w + 0.5);
-  if (o.support > kMaxSupport) {
-    set_last_error("uammd_dpstokes_create: support = %d: the window takes at most %d nodes per axis (w <= %g)", o.support, kMaxSupport,
-                   kMaxSupport + 0.49);
+  if (o.support > dp::kMaxSupport) {
+    set_last_error("uammd_dpstokes_create: support = %d: the window takes at most %d nodes per axis (w <= %g)", o.support, dp::kMaxSupport,
+                   dp::kMaxSupport + 0.49);
     return -2;
   }
   if (o.support < 1 || o.support > std::min(p.nx, p.ny)) {
@@ -732,25 +583,13 @@ struct DPStokes {
   DeviceBuffer fields, wall, constants, zeroMode, counters;
   DeviceBuffer rec, cellrec;
   bool ran = false;
-  // option time_stages: device events between the stage launches of a run (uammd_dpstokes_stage_times)
-  bool timeStages = false;
-  hipEvent_t stageEvent[dps::kStages + 1] = {};
-  int stageMarks = 0;
+  StageTimer<dps::kStages> timer;  // option time_stages (uammd_dpstokes_stage_times)
   ~DPStokes() {
-    for (hipEvent_t e : stageEvent)
-      if (e) (void)hipEventDestroy(e);
     if (fct) uammd_fct_destroy(fct);
     if (bvp) uammd_bvp_destroy(bvp);
     if (bvpZero) uammd_bvp_destroy(bvpZero);
   }
 };
-
-template <class U> static int dps_upload(DeviceBuffer &b, const std::vector<double> &v) {
-  std::vector<U> tmp(v.begin(), v.end());
-  if (int e = b.reserve(std::max<size_t>(tmp.size(), 1) * sizeof(U))) return e;
-  if (!tmp.empty()) UH_CHECK(hipMemcpy(b.ptr, tmp.data(), tmp.size() * sizeof(U), hipMemcpyHostToDevice));
-  return 0;
-}
 
 template <class U> static ChebGridBM<U> dps_grid(const DPStokes *h) {
   const auto &p = h->par;
@@ -758,7 +597,7 @@ template <class U> static ChebGridBM<U> dps_grid(const DPStokes *h) {
   ChebGridBM<U> g;
   g.nx = c.cells[0]; g.ny = c.cells[1]; g.nz = c.cells[2];
   g.support = c.support;
-  g.Lx = (U)p.Lx; g.Ly = (U)p.Ly; g.H = (U)p.H;
+  g.Lx = (U)p.Lx; g.Ly = (U)p.Ly; g.span = (U)p.H;
   g.hx = (U)c.hx; g.hy = (U)c.hy;
   g.invhx = (U)(1.0 / c.hx); g.invhy = (U)(1.0 / c.hy);
   g.alpha = (U)p.alpha; g.az = (U)c.az;
@@ -778,30 +617,23 @@ template <class U> static int dps_build(DPStokes *h) {
   h->nsys = nsys;
   h->nz = nz;
   const double Hh = 0.5 * p.H;
-  std::vector<double> zp(nz), qw(nz), k(nsys), kx(nsys), ky(nsys), tfi(nsys), tsi(nsys), bfi(nsys), bsi(nsys);
-  for (int i = 0; i < nz; ++i) {
-    zp[i] = Hh * std::cos(M_PI * i / (nz - 1));
-    qw[i] = Hh * dps::clencurt(i, nz - 1) * (c.hx * c.hy);
-  }
+  std::vector<double> zp, qw, k(nsys), kx(nsys), ky(nsys), tfi(nsys), tsi(nsys), bfi(nsys), bsi(nsys);
+  dp::chebyshev_planes(nz, Hh, c.hx, c.hy, zp, qw);
   for (int s = 0; s < nsys; ++s) {
-    dps::wave_vector(s, nx, ny, p.Lx, p.Ly, kx[s], ky[s], k[s]);
-    const bool nonzero = k[s] != 0;  // initialization.cu:74-96
-    tfi[s] = nonzero ? Hh : 0.0;
-    tsi[s] = nonzero ? Hh * Hh * k[s] : 1.0;
-    bfi[s] = nonzero ? Hh : 0.0;
-    bsi[s] = nonzero ? -Hh * Hh * k[s] : 1.0;
+    dp::wave_vector(s, nx, ny, p.Lx, p.Ly, kx[s], ky[s], k[s]);
+    dp::bvp_boundary_factors(k[s], Hh, tfi[s], tsi[s], bfi[s], bsi[s]);
   }
-  int e = dps_upload<U>(h->zplane, zp);
-  if (!e) e = dps_upload<U>(h->qw, qw);
-  if (!e) e = dps_upload<U>(h->kmod, k);
-  if (!e) e = dps_upload<U>(h->kxPaired, kx);
-  if (!e) e = dps_upload<U>(h->kyPaired, ky);
+  int e = upload<U>(h->zplane, zp);
+  if (!e) e = upload<U>(h->qw, qw);
+  if (!e) e = upload<U>(h->kmod, k);
+  if (!e) e = upload<U>(h->kxPaired, kx);
+  if (!e) e = upload<U>(h->kyPaired, ky);
   if (e) return e;
   if (p.mode != dps::kNone) {  // what the correction reads, in double
-    e = dps_upload<double>(h->zplaneD, zp);
-    if (!e) e = dps_upload<double>(h->kmodD, k);
-    if (!e) e = dps_upload<double>(h->kxPairedD, kx);
-    if (!e) e = dps_upload<double>(h->kyPairedD, ky);
+    e = upload<double>(h->zplaneD, zp);
+    if (!e) e = upload<double>(h->kmodD, k);
+    if (!e) e = upload<double>(h->kxPairedD, kx);
+    if (!e) e = upload<double>(h->kyPairedD, ky);
     if (e) return e;
     if (p.mode == dps::kSlit) {
       std::vector<dps::cplx> inv;
@@ -813,7 +645,7 @@ template <class U> static int dps_build(DPStokes *h) {
           flat[2 * ((size_t)n * nsys + s)] = inv[(size_t)64 * s + n].real();
           flat[2 * ((size_t)n * nsys + s) + 1] = inv[(size_t)64 * s + n].imag();
         }
-      if (int e2 = dps_upload<double>(h->invA, flat)) return e2;
+      if (int e2 = upload<double>(h->invA, flat)) return e2;
     }
     double f[4];
     dps::zero_mode_factors(p.mode, f);
@@ -834,54 +666,40 @@ template <class U> static int dps_build(DPStokes *h) {
 // DPStokes::Mdot (DPStokesSlab.cuh:220-251).  d_mf == nullptr stops after the corrected Chebyshev coefficients (computeAverageVelocity).
 template <class U>
 static int dps_run(DPStokes *h, const U *d_pos, int ps, const U *d_force, int fs, int N, U *d_mf, hipStream_t st) {
-  using T2 = typename dps::Vec<U>::T2;
+  using T2 = typename VecOf<U>::T2;
   const auto &p = h->par;
   const ChebGridBM<U> g = dps_grid<U>(h);
   const int nsys = h->nsys, nz = h->nz, mode = p.mode;
   const size_t field = (size_t)nsys * nz;
-  if (int e = h->rec.reserve(sizeof(dps::rec4<U>) * (size_t)N)) return e;
+  if (int e = h->rec.reserve(sizeof(typename VecOf<U>::T4) * (size_t)N)) return e;
   if (int e = h->cellrec.reserve(sizeof(int4) * (size_t)N)) return e;
   // fields: 0, 1 the spectra of (fx + i fy), (fz); 2, 3 the spread grids; 4-6 right-hand sides; 7-9 second derivatives; 10 pressure;
   // 11-13 velocities.  Later: the correction at the planes in 6-9 and in Chebyshev space in 2-5; the packed output in 6, 7 and its
   // inverse transforms in 8, 9.
   T2 *F[dps::kFields];
   for (int i = 0; i < dps::kFields; ++i) F[i] = (T2 *)h->fields.ptr + field * i;
-  const dps::rec4<U> *rec = (const dps::rec4<U> *)h->rec.ptr;
+  const typename VecOf<U>::T4 *rec = (const typename VecOf<U>::T4 *)h->rec.ptr;
   const int4 *cellrec = (const int4 *)h->cellrec.ptr;
-  h->stageMarks = 0;
-  auto mark = [&]() -> int {  // one event after every stage; nothing is recorded, created or waited for unless time_stages is set
-    if (!h->timeStages) return 0;
-    hipEvent_t &e = h->stageEvent[h->stageMarks];
-    if (!e) UH_CHECK(hipEventCreate(&e));
-    UH_CHECK(hipEventRecord(e, st));
-    ++h->stageMarks;
-    return 0;
-  };
+  h->timer.reset();
+  auto mark = [&]() { return h->timer.mark(st); };
   if (int e = mark()) return e;
   // (1)
   UH_CHECK(hipMemsetAsync(h->counters.ptr, 0, 8 * sizeof(unsigned), st));
   hipLaunchKernelGGL((k_dps_classify<U>), dim3((N + 255) / 256), dim3(256), 0, st, d_pos, ps, d_force, fs, N, g, (U)(0.5 * p.H),
-                     (dps::rec4<U> *)h->rec.ptr, (int4 *)h->cellrec.ptr, (unsigned *)h->counters.ptr);
+                     (typename VecOf<U>::T4 *)h->rec.ptr, (int4 *)h->cellrec.ptr, (unsigned *)h->counters.ptr);
   if (int e = mark()) return e;
   // (2)
   if (h->simpleSpread) {
     UH_CHECK(hipMemsetAsync(F[2], 0, sizeof(T2) * field * 2, st));
-    hipLaunchKernelGGL((k_dps_spread_simple<U>), dim3((N + 63) / 64), dim3(64), 0, st, rec, cellrec, d_force, fs, N, g, (U *)F[2], (U *)F[3]);
+    hipLaunchKernelGGL((k_dp_spread_simple<U, ChebGridBM<U>, DpsSource<U>>), dim3((N + 63) / 64), dim3(64), 0, st, rec, cellrec, N, g,
+                       DpsSource<U>{d_force, fs}, (U *)F[2], (U *)F[3]);
   } else {
-    constexpr int T = dps::kTile;
-    const dim3 grid(((g.nx + T - 1) / T) * ((g.ny + T - 1) / T), (nz + T - 1) / T);
-    hipLaunchKernelGGL((k_dps_spread_owner<U>), grid, dim3(64), 0, st, rec, cellrec, d_force, fs, N, g, (const unsigned *)h->counters.ptr,
-                       (U)h->cfg.wmax, F[2], F[3]);
+    hipLaunchKernelGGL((k_dps_spread_owner<U>), dp_owner_grid(g.nx, g.ny, nz), dim3(64), 0, st, rec, cellrec, d_force, fs, N, g,
+                       (const unsigned *)h->counters.ptr, (U)h->cfg.wmax, F[2], F[3]);
   }
   UH_CHECK(hipGetLastError());
   if (int e = mark()) return e;
-  auto fctRun = [&](bool planes, const T2 *in, T2 *out, int dir) -> int {
-    if (sizeof(U) == sizeof(double))
-      return planes ? uammd_fct_fourier_chebyshev_f64(h->fct, (const double *)in, (double *)out, dir, st)
-                    : uammd_fct_chebyshev_f64(h->fct, (const double *)in, (double *)out, dir, st);
-    return planes ? uammd_fct_fourier_chebyshev(h->fct, (const float *)in, (float *)out, dir, st)
-                  : uammd_fct_chebyshev(h->fct, (const float *)in, (float *)out, dir, st);
-  };
+  auto fctRun = [&](bool planes, const T2 *in, T2 *out, int dir) { return fct_run<U>(h->fct, planes, in, out, dir, st); };
   // (3)
   if (int e = fctRun(true, F[2], F[0], UAMMD_FCT_FORWARD)) return e;
   if (int e = mark()) return e;
@@ -937,7 +755,8 @@ static int dps_run(DPStokes *h, const U *d_pos, int ps, const U *d_force, int fs
   if (int e = mark()) return e;
   if (int e = fctRun(true, F[7], F[9], UAMMD_FCT_INVERSE)) return e;
   if (int e = mark()) return e;
-  hipLaunchKernelGGL((k_dps_gather<U>), dim3((N + 3) / 4), dim3(256), 0, st, rec, cellrec, N, g, (const T2 *)F[8], (const T2 *)F[9], d_mf);
+  hipLaunchKernelGGL((k_dp_gather<U, ChebGridBM<U>, 3, DpsSink<U>, U>), dim3((N + 3) / 4), dim3(256), 0, st, rec, cellrec, N, g, (const T2 *)F[8],
+                     (const T2 *)F[9], d_mf);
   UH_CHECK(hipGetLastError());
   if (int e = mark()) return e;
   return 0;
@@ -946,10 +765,7 @@ static int dps_run(DPStokes *h, const U *d_pos, int ps, const U *d_force, int fs
 static int dps_check(DPStokes *h, bool wantDouble, const void *pos, int ps, const void *force, int fs, const void *torque, int N, const char *who) {
   if (torque) { set_last_error("[DPStokes] Torques are not implemented (%s: pass a null torque pointer)", who); return -3; }
   if (!h) { set_last_error("%s: null handle", who); return -1; }
-  if (h->doublePrecision != wantDouble) {
-    set_last_error("%s: the handle was created for %s precision", who, h->doublePrecision ? "double" : "single");
-    return -1;
-  }
+  if (int e = dp_check_precision(h->doublePrecision, wantDouble, who)) return e;
   if (N < 0) { set_last_error("%s: numberParticles = %d", who, N); return -1; }
   if ((ps != 3 && ps != 4) || (fs != 3 && fs != 4)) { set_last_error("%s: positions and forces are rows of 3 or 4 reals (got %d, %d)", who, ps, fs); return -1; }
   if (N > 0 && (!pos || !force)) { set_last_error("%s: null argument", who); return -1; }
@@ -1086,10 +902,7 @@ template <class U> static int dpsi_step(DPStokesIntegrator *I, U *d_pos, int ps,
 
 static int dpsi_check(DPStokesIntegrator *I, bool wantDouble, const void *pos, int ps, int N, const char *who) {
   if (!I) { set_last_error("%s: null handle", who); return -1; }
-  if (I->solver->doublePrecision != wantDouble) {
-    set_last_error("%s: the handle was created for %s precision", who, I->solver->doublePrecision ? "double" : "single");
-    return -1;
-  }
+  if (int e = dp_check_precision(I->solver->doublePrecision, wantDouble, who)) return e;
   if (N < 0) { set_last_error("%s: numberParticles = %d", who, N); return -1; }
   if (ps != 3 && ps != 4) { set_last_error("%s: positions are rows of 3 or 4 reals (got %d)", who, ps); return -1; }
   if (N > 0 && !pos) { set_last_error("%s: null argument", who); return -1; }
@@ -1134,7 +947,7 @@ int uammd_dpstokes_set_option(uammd_dpstokes *h_, const char *name, int value) {
   if (!h || !name) { set_last_error("uammd_dpstokes_set_option: null argument"); return -1; }
   const std::string n(name);
   if (n == "simple_spread") { h->simpleSpread = value != 0; return 0; }
-  if (n == "time_stages") { h->timeStages = value != 0; h->stageMarks = 0; return 0; }
+  if (n == "time_stages") { h->timer.enable(value != 0); return 0; }
   set_last_error("uammd_dpstokes_set_option: unknown option %s", name);
   return -1;
 }
@@ -1186,10 +999,7 @@ int uammd_dpstokes_average_velocity_f64(uammd_dpstokes *h, const double *d_pos, 
 static int dps_fluid_cheb(uammd_dpstokes *h_, bool wantDouble, void *d_out, const char *who) {
   DPStokes *h = reinterpret_cast<DPStokes *>(h_);
   if (!h || !d_out) { set_last_error("%s: null argument", who); return -1; }
-  if (h->doublePrecision != wantDouble) {
-    set_last_error("%s: the handle was created for %s precision", who, h->doublePrecision ? "double" : "single");
-    return -1;
-  }
+  if (int e = dp_check_precision(h->doublePrecision, wantDouble, who)) return e;
   if (!h->ran) { set_last_error("%s: nothing has run on this handle", who); return -1; }
   UH_CHECK(hipDeviceSynchronize());  // the last run may have used any stream
   const size_t real = wantDouble ? sizeof(double) : sizeof(float);
@@ -1216,17 +1026,7 @@ int uammd_dpstokes_outside_count(uammd_dpstokes *h_, int *count) {
 int uammd_dpstokes_stage_times(uammd_dpstokes *h_, double *ms) {
   DPStokes *h = reinterpret_cast<DPStokes *>(h_);
   if (!h || !ms) { set_last_error("uammd_dpstokes_stage_times: null argument"); return -1; }
-  if (!h->timeStages || h->stageMarks < 2) { set_last_error("uammd_dpstokes_stage_times: set option time_stages before the call"); return -1; }
-  UH_CHECK(hipEventSynchronize(h->stageEvent[h->stageMarks - 1]));
-  for (int i = 0; i < dps::kStages; ++i) {
-    ms[i] = 0;
-    if (i + 1 < h->stageMarks) {
-      float t = 0;
-      UH_CHECK(hipEventElapsedTime(&t, h->stageEvent[i], h->stageEvent[i + 1]));
-      ms[i] = t;
-    }
-  }
-  return 0;
+  return h->timer.times(ms, "uammd_dpstokes_stage_times");
 }
 
 int uammd_dpstokes_integrator_create(const uammd_dpstokes_parameters *par, const uammd_dpstokes_integrator_parameters *ipar, int double_precision,

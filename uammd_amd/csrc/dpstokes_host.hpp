@@ -8,6 +8,7 @@
 //         system with k = 0 and the boundary factors below.
 #pragma once
 #include "bvp_host.hpp"
+#include "dp_slab_host.hpp"
 
 #include <complex>
 #include <utility>
@@ -59,19 +60,8 @@ inline bool invert(int n, cplx *A, cplx *inv) {
   return true;
 }
 
-// system s = i + nx j of a full plane: the modulus of its wave vector, and the wave vector with a zero on an unpaired index
-inline void wave_vector(int s, int nx, int ny, double Lx, double Ly, double &kx, double &ky, double &k) {
-  const int i = s % nx, j = s / nx;
-  kx = 2 * M_PI / Lx * (i - nx * (i >= nx / 2 + 1));
-  ky = 2 * M_PI / Ly * (j - ny * (j >= ny / 2 + 1));
-  k = std::sqrt(kx * kx + ky * ky);
-  if (nx % 2 == 0 && i == nx / 2) kx = 0.0;
-  if (ny % 2 == 0 && j == ny / 2) ky = 0.0;
-}
-inline int mirror(int s, int nx, int ny) {  // the system of the opposite wave vector
-  const int i = s % nx, j = s / nx;
-  return (i ? nx - i : 0) + nx * (j ? ny - j : 0);
-}
+using dp::mirror;
+using dp::wave_vector;
 
 // out[64 s + 8 r + c]: the inverse of wave number s; the k = 0 block stays zero (the zero mode has a solve of its own).
 // Returns 0, or -2 with a message that names the wave number at fault.
