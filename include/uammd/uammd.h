@@ -26,7 +26,9 @@
 // four BD schemes — every class the reference's unit tests (test/CMakeLists.txt:19-28, minus the doubly periodic and Chebyshev ones) and its
 // double-precision acceptance programs of path B (test/BDHI/{FCM, quasi2D, Lanczos_Cholesky}) construct.  The classes whose backend exists in
 // single precision only (CellList, VerletList, PairForces, VerletNVT, FIB, ICM, Comm) are not declared in that build: their
-// forwarding headers stop the compilation with a message instead of silently computing in float.
+// forwarding headers stop the compilation with a message instead of silently computing in float.  (For the cell list, the LJ traversal,
+// VerletNVT and VerletNVE the double backend now exists behind the C ABI — the "Path A in double" block of uammd_hip.h — and routing these
+// headers to it is a separate step.)
 //
 // This header is plain host C++14: compile with any C++ compiler,
 //     g++ -std=c++14 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude main.cpp \

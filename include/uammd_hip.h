@@ -1191,6 +1191,82 @@ int uammd_bdhi_cholesky_bdw_f64(uammd_bdhi_cholesky_f64 *h, const double *d_pos,
                                 void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Path A in double (uammd_amd/csrc/md_f64.hip): the cell list, the Lennard-Jones traversal and the Verlet integrators with
+ * real = double.  The same reference interfaces as the single-precision blocks above:
+ *   CellList::createUpdateGrid / CellListBase::update / getCellList   Interactor/NeighbourList/CellList.cuh:100-126,149-182,
+ *                                                                     CellList/CellListBase.cuh:68-94,124-172,210-230
+ *   ParticleSorter hash, stable sort, reorder                         utils/ParticleSorter.cuh:102-111,178-187,303-321
+ *   transverseWithNeighbourContainer + Radial<LJFunctor>              Interactor/NeighbourList/common.cuh:10-34,
+ *                                                                     Potential/RadialPotential.cuh:107-127, Potential.cuh:37-82
+ *   NBody::transverse (boxes of at most 3 cut-offs)                   Interactor/NBodyBase.cuh:46-159, PairForces.cu:43-68
+ *   VerletNVT GronbechJensen / Basic, initialVelocities, energy       Integrator/VerletNVT/GronbechJensen.cu:28-62, Basic.cu:12-29,86-114,173-207
+ *   VerletNVE                                                         Integrator/VerletNVE.cu:64-85
+ * Positions / forces are real4 = double[4N], velocities real3 = double[3N].  Every particle sums its pairs in the reference's neighbour
+ * order (the 27 cells in common.cuh order, members in sorted order).  The UAMMD-shaped C++ headers do not route here yet: they refuse
+ * -DDOUBLE_PRECISION as before.  Single precision only: the Verlet list, DPD / SPH / bonded / MC, the tile traversal, the fused MD
+ * step, the slab drivers, num_owned ghosts and the profiling hooks.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uammd_celllist_f64 uammd_celllist_f64; /* opaque; owns index/hash/sortPos/cellStart/cellEnd */
+/* uammd_celllist_data field for field, with double positions and box */
+typedef struct {
+  const unsigned int *d_cellStart;
+  const int *d_cellEnd;
+  const double *d_sortPos; /* real4[N] */
+  const int *d_groupIndex;
+  const unsigned int *d_sortHash;
+  int cellDim[3];
+  double boxSize[3];
+  int periodic[3];
+  unsigned int VALID_CELL;
+  int numberParticles;
+} uammd_celllist_data_f64;
+int uammd_celllist_create_f64(uammd_celllist_f64 **out);
+int uammd_celllist_destroy_f64(uammd_celllist_f64 *h);
+/* uammd_celllist_create_grid with the division and the truncation in double (host only) */
+int uammd_celllist_create_grid_f64(const double L[3], const int periodic[3], const double cutOff[3], int cellDim_out[3], double L_out[3],
+                                   int periodic_out[3]);
+/* hash (Morton key of the position's cell) -> stable sort of (key, index) on the key's bits -> gather of the rows -> cell tables.
+ * d_pos is real4[N] in double; numberParticles = 0 is a no-op.  A NaN position or a particle outside a non-periodic box has no cell: it is
+ * left out of the tables (it sorts behind every cell) and raises the list's host-mapped flag; the next update / get / traversal on the
+ * handle fails with the reference's message, uammd_celllist_check_errors_f64 synchronises `stream` and reports at once. */
+int uammd_celllist_update_f64(uammd_celllist_f64 *h, const double *d_pos, int numberParticles, const double L[3], const int periodic[3],
+                              const int cellDim[3], void *stream);
+int uammd_celllist_get_f64(uammd_celllist_f64 *h, uammd_celllist_data_f64 *out);
+int uammd_celllist_check_errors_f64(uammd_celllist_f64 *h, void *stream);
+
+/* LJFunctor::PairParameters and processPairParameters (Potential/Potential.cuh:31-35,66-82) in double, host */
+typedef struct { double cutOff2, sigma2, epsilonDivSigma2, shift; } uammd_lj_pair_parameters_f64;
+int uammd_lj_process_pair_parameters_f64(double cutOff, double sigma, double epsilon, int shift, uammd_lj_pair_parameters_f64 *out);
+/* `algo` of uammd_lj_transverse_celllist_f64: UAMMD_LJ_ALGO_AUTO, UAMMD_LJ_ALGO_GENERAL or */
+#define UAMMD_LJ_ALGO_SCAN32 11 /* GENERAL's pair evaluation fed by a distance scan over a single-precision image of the sorted positions
+                                   (a strict superset of the pairs inside the cut-off; the evaluation applies the exact test in double):
+                                   the same bits as GENERAL.  Grids the image does not cover (another box than the list's, a periodic
+                                   direction with fewer than 5 cells) run GENERAL */
+/* Arguments as uammd_lj_transverse_celllist.  With ntypes > 1 the kernels read the table's largest cut-off themselves: a table may be
+ * rewritten in place between calls without telling the library. */
+int uammd_lj_transverse_celllist_f64(uammd_celllist_f64 *h, const uammd_lj_pair_parameters_f64 *d_paramTable, int ntypes,
+                                     const double boxL[3], const int boxPeriodic[3], double *d_force, double *d_energy, double *d_virial,
+                                     const int *d_globalIndex, int algo, void *stream);
+int uammd_lj_transverse_nbody_f64(const double *d_pos, int numberParticles, const uammd_lj_pair_parameters_f64 *d_paramTable, int ntypes,
+                                  const double boxL[3], const int boxPeriodic[3], double *d_force, double *d_energy, double *d_virial,
+                                  const int *d_globalIndex, void *stream);
+
+/* The integrators of the single-precision block with double for every float.  The thermostat's Gaussians are Saru's single-precision
+ * Box-Muller pair promoted to double, as in the reference's double build (third_party/saruprng.cuh:115-128; uammd_bd_scheme_step_f64). */
+int uammd_verletnvt_gj_f64(int step, double *d_pos, double *d_vel, double *d_force, const double *d_mass, double defaultMass,
+                           const int *d_index, int numberParticles, double dt, double friction, int is2D, double noiseAmplitude,
+                           unsigned int stepNum, unsigned int seed, void *stream);
+int uammd_verletnvt_basic_f64(int step, double *d_pos, double *d_vel, double *d_force, const double *d_mass, double defaultMass,
+                              const int *d_index, int numberParticles, double dt, double friction, int is2D, double noiseAmplitude,
+                              unsigned int stepNum, unsigned int seed, void *stream);
+int uammd_verletnve_f64(int step, double *d_pos, double *d_vel, const double *d_force, const double *d_mass, double defaultMass,
+                        const int *d_index, int numberParticles, double dt, int is2D, void *stream);
+int uammd_verletnvt_initial_velocities_f64(double *d_vel, const int *d_index, double velAmplitude, int is2D, int numberParticles,
+                                           unsigned int seed, void *stream);
+int uammd_sum_kinetic_energy_f64(const double *d_vel, double *d_energy, const double *d_mass, double defaultMass, const int *d_index,
+                                 int numberParticles, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bonded interactions.  Replaces BondedForces<BondType, particlesPerBond> (Interactor/BondedForces.{cuh,cu}),
  * AngularBondedForces.cuh and TorsionalBondedForces.cuh for the built-in kinds.  Every particle with bonds sums, in registration
  * order, each bond it is a member of and adds the result to its own force / energy / virial: no atomics, the same bits on every run.

@@ -25,6 +25,17 @@ class CellListData(C.Structure):
                 ("numberParticles", C.c_int)]
 
 
+class LJPairParameters64(C.Structure):
+    _fields_ = [("cutOff2", C.c_double), ("sigma2", C.c_double), ("epsilonDivSigma2", C.c_double), ("shift", C.c_double)]
+
+
+class CellListData64(C.Structure):
+    _fields_ = [("d_cellStart", C.c_void_p), ("d_cellEnd", C.c_void_p), ("d_sortPos", C.c_void_p),
+                ("d_groupIndex", C.c_void_p), ("d_sortHash", C.c_void_p), ("cellDim", C.c_int * 3),
+                ("boxSize", C.c_double * 3), ("periodic", C.c_int * 3), ("VALID_CELL", C.c_uint),
+                ("numberParticles", C.c_int)]
+
+
 class VerletListData(C.Structure):
     _fields_ = [("d_neighbourList", C.c_void_p), ("d_numberNeighbours", C.c_void_p), ("d_sortPos", C.c_void_p),
                 ("d_groupIndex", C.c_void_p), ("particleStride", C.c_int), ("maxNeighboursPerParticle", C.c_int),
@@ -437,6 +448,21 @@ SIGNATURES = {
     "uammd_bdhi_cholesky_setup_step_f64": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "uammd_bdhi_cholesky_mf_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "uammd_bdhi_cholesky_bdw_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    # path A in double (md_f64.hip)
+    "uammd_celllist_create_f64": (_i, [C.POINTER(_vp)]),
+    "uammd_celllist_destroy_f64": (_i, [_vp]),
+    "uammd_celllist_create_grid_f64": (_i, [_d3, _i3, _d3, _i3, _d3, _i3]),
+    "uammd_celllist_update_f64": (_i, [_vp, _vp, _i, _d3, _i3, _i3, _vp]),
+    "uammd_celllist_get_f64": (_i, [_vp, C.POINTER(CellListData64)]),
+    "uammd_celllist_check_errors_f64": (_i, [_vp, _vp]),
+    "uammd_lj_process_pair_parameters_f64": (_i, [_d, _d, _d, _i, C.POINTER(LJPairParameters64)]),
+    "uammd_lj_transverse_celllist_f64": (_i, [_vp, _vp, _i, _d3, _i3, _vp, _vp, _vp, _vp, _i, _vp]),
+    "uammd_lj_transverse_nbody_f64": (_i, [_vp, _i, _vp, _i, _d3, _i3, _vp, _vp, _vp, _vp, _vp]),
+    "uammd_verletnvt_gj_f64": (_i, [_i, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _d, _i, _d, _u, _u, _vp]),
+    "uammd_verletnvt_basic_f64": (_i, [_i, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _d, _i, _d, _u, _u, _vp]),
+    "uammd_verletnve_f64": (_i, [_i, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _i, _vp]),
+    "uammd_verletnvt_initial_velocities_f64": (_i, [_vp, _vp, _d, _i, _i, _u, _vp]),
+    "uammd_sum_kinetic_energy_f64": (_i, [_vp, _vp, _vp, _d, _vp, _i, _vp]),
 }
 
 MATVEC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)

@@ -322,3 +322,244 @@ class BD:
         else:
             self._eval(pos)
             self._advance(pos, 0, original_index if self.scheme == 3 else None)
+
+
+# ---- path A in double (md_f64.hip): cell list, Lennard-Jones, Verlet integrators ------------------------------------------------------
+class Box:
+    """Box (utils/Box.cuh) with double sides."""
+
+    def __init__(self, L, periodic=(True, True, True)):
+        self.boxSize = np.broadcast_to(np.asarray(L, dtype=np.float64), (3,)).copy()
+        self.periodic = [bool(p) for p in np.broadcast_to(np.asarray(periodic), (3,))]
+
+    def __eq__(self, o):
+        return isinstance(o, Box) and np.array_equal(self.boxSize, o.boxSize) and list(self.periodic) == list(o.periodic)
+
+
+def _check_rows(t, width):
+    assert t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == width, "expected a contiguous float64 [N, %d]" % width
+
+
+class CellList:
+    """The NeighbourList concept on double positions [N, 4] (uammd_celllist_*_f64): update(box, cutoff, pos) + getCellList +
+    transverse_lj.  No ParticleData behind it: the caller says when the positions changed by calling update again."""
+    GENERAL, SCAN32, AUTO = 1, 11, 0
+
+    def __init__(self):
+        self.lib = _lib.load()
+        h = C.c_void_p()
+        check(self.lib.uammd_celllist_create_f64(C.byref(h)))
+        self.h = h
+        self.N = 0
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.uammd_celllist_destroy_f64(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def check_errors(self):
+        check(self.lib.uammd_celllist_check_errors_f64(self.h, _stream()))
+
+    @staticmethod
+    def create_update_grid(box, cutoff):
+        """CellList::createUpdateGrid (CellList.cuh:100-126) in double: (cellDim, the box the list is built on)."""
+        lib = _lib.load()
+        cd, Lo, po = _i3(0), _d3(0.0), _i3(0)
+        check(lib.uammd_celllist_create_grid_f64(_d3(box.boxSize), _i3([int(p) for p in box.periodic]), _d3(cutoff), cd, Lo, po))
+        return list(cd), Box(list(Lo), [bool(p) for p in po])
+
+    def update_grid(self, pos, box, cellDim):
+        """CellListBase::update(pos, N, grid, st) (CellListBase.cuh:124-140)."""
+        _check_rows(pos, 4)
+        self.N = pos.shape[0]
+        self._pos_ref = pos
+        check(self.lib.uammd_celllist_update_f64(self.h, _ptr(pos), self.N, _d3(box.boxSize), _i3([int(p) for p in box.periodic]),
+                                                 _i3(cellDim), _stream()))
+
+    def update(self, box, cutoff, pos):
+        """CellList::update(box, cutOff, st) (CellList.cuh:149-163); the list is rebuilt on every call."""
+        cd, ubox = self.create_update_grid(box, cutoff)
+        self.update_grid(pos, ubox, cd)
+
+    def getCellList(self):
+        d = _lib.CellListData64()
+        check(self.lib.uammd_celllist_get_f64(self.h, C.byref(d)))
+        return d
+
+    @staticmethod
+    def _wrap(ptr, shape, dtype):
+        if int(np.prod(shape)) == 0:
+            return torch.empty(shape, dtype=dtype, device="cuda")
+
+        class _Raw:   # zero-copy view of library-owned device memory through __cuda_array_interface__
+            pass
+        r = _Raw()
+        r.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": {torch.float64: "<f8", torch.int32: "<i4"}[dtype],
+                                      "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(r, device="cuda")
+
+    def to_host(self):
+        """Copies the list to numpy (tests): hash, index, sortPos, cellStart, cellEnd, VALID_CELL."""
+        d = self.getCellList()
+        n = d.numberParticles
+        nc = d.cellDim[0] * d.cellDim[1] * d.cellDim[2]
+        torch.cuda.synchronize()
+        return dict(index=self._wrap(d.d_groupIndex, (n,), torch.int32).cpu().numpy(),
+                    hash=self._wrap(d.d_sortHash, (n,), torch.int32).cpu().numpy().view(np.uint32),
+                    sortPos=self._wrap(d.d_sortPos, (n, 4), torch.float64).cpu().numpy(),
+                    cellStart=self._wrap(d.d_cellStart, (nc,), torch.int32).cpu().numpy().view(np.uint32),
+                    cellEnd=self._wrap(d.d_cellEnd, (nc,), torch.int32).cpu().numpy(),
+                    validCell=int(d.VALID_CELL), cellDim=np.array(list(d.cellDim), np.int32),
+                    L=np.array(list(d.boxSize), np.float64), periodic=np.array(list(d.periodic), np.int32))
+
+    def transverse_lj(self, param_table, ntypes, box, force=None, energy=None, virial=None, global_index=None, algo=0):
+        check(self.lib.uammd_lj_transverse_celllist_f64(self.h, _ptr(param_table), int(ntypes), _d3(box.boxSize),
+                                                        _i3([int(p) for p in box.periodic]), _ptr(force), _ptr(energy), _ptr(virial),
+                                                        _ptr(global_index), int(algo), _stream()))
+
+
+class LJ:
+    """Potential::LJ = Radial<LJFunctor> with BasicParameterHandler in double; the type table grows as md._LJ's does."""
+
+    class InputPairParameters:
+        def __init__(self, cutOff=2.5, sigma=1.0, epsilon=1.0, shift=False):
+            self.cutOff, self.sigma, self.epsilon, self.shift = cutOff, sigma, epsilon, shift
+
+    def __init__(self):
+        self.lib = _lib.load()
+        self.ntypes = 1
+        self.cutOff = 0.0
+        self.table = np.zeros((1, 4), np.float64)
+        self._dev = None
+
+    def setPotParameters(self, ti, tj, p):
+        self.cutOff = max(float(p.cutOff), self.cutOff)
+        new = max(self.ntypes, ti + 1, tj + 1)
+        if new != self.ntypes:
+            tmp = np.zeros((new * new, 4), np.float64)
+            for i in range(self.ntypes):
+                for j in range(self.ntypes):
+                    tmp[i + new * j] = self.table[i + self.ntypes * j]
+            self.table, self.ntypes = tmp, new
+        out = _lib.LJPairParameters64()
+        check(self.lib.uammd_lj_process_pair_parameters_f64(float(p.cutOff), float(p.sigma), float(p.epsilon), int(bool(p.shift)), C.byref(out)))
+        row = np.array([out.cutOff2, out.sigma2, out.epsilonDivSigma2, out.shift], np.float64)
+        self.table[ti + self.ntypes * tj] = row
+        if ti != tj:
+            self.table[tj + self.ntypes * ti] = row
+        self._dev = None
+
+    def getCutOff(self):
+        return self.cutOff
+
+    def device_table(self):
+        if self._dev is None:
+            self._dev = torch.from_numpy(self.table.copy()).cuda()
+        return self._dev
+
+
+class PairForcesLJ:
+    """PairForces<Potential::LJ, CellList> in double (PairForces.cu:43-78): the cell list unless the box is at most 3 cut-offs in every
+    direction, then all pairs.  sum() ACCUMULATES into the arrays it is given (Transverser::set does +=)."""
+
+    def __init__(self, box, potential, algo=0):
+        self.lib = _lib.load()
+        self.box, self.pot, self.algo, self.nl = box, potential, algo, None
+
+    def sum(self, pos, force=None, energy=None, virial=None):
+        _check_rows(pos, 4)
+        rc = float(self.pot.getCutOff())
+        L = self.box.boxSize
+        tbl = self.pot.device_table()
+        if L[0] <= 3 * rc and L[1] <= 3 * rc and L[2] <= 3 * rc:     # PairForces.cu:43-53
+            check(self.lib.uammd_lj_transverse_nbody_f64(_ptr(pos), pos.shape[0], _ptr(tbl), self.pot.ntypes, _d3(L),
+                                                         _i3([int(p) for p in self.box.periodic]), _ptr(force), _ptr(energy), _ptr(virial),
+                                                         None, _stream()))
+            return
+        if self.nl is None:
+            self.nl = CellList()
+        self.nl.update(self.box, rc, pos)
+        self.nl.transverse_lj(tbl, self.pot.ntypes, self.box, force, energy, virial, None, self.algo)
+
+
+def initVelocities(vel, velAmplitude, seed, is2D=False, index=None):
+    """VerletNVT::Basic_ns::initialVelocities (Basic.cu:12-29) on vel double[N, 3]; index: the group's members (None = everybody)."""
+    _check_rows(vel, 3)
+    n = vel.shape[0] if index is None else index.shape[0]
+    check(_lib.load().uammd_verletnvt_initial_velocities_f64(_ptr(vel), _ptr(index), float(velAmplitude), int(bool(is2D)), n,
+                                                             int(seed) & 0xFFFFFFFF, _stream()))
+
+
+def sumKineticEnergy(vel, energy, mass=None, defaultMass=1.0, index=None):
+    """energy[i] += m |v|^2 / 2 (Basic.cu:173-207); defaultMass > 0 wins over the mass array."""
+    _check_rows(vel, 3)
+    n = vel.shape[0] if index is None else index.shape[0]
+    check(_lib.load().uammd_sum_kinetic_energy_f64(_ptr(vel), _ptr(energy), _ptr(mass), float(defaultMass), _ptr(index), n, _stream()))
+
+
+class VerletNVT:
+    """VerletNVT::GronbechJensen / Basic in double (Integrator/VerletNVT.cuh): forwardTime(pos, vel, force, interactors) with interactors
+    that offer sum(pos, force).  seed: the reference takes the System generator's third draw."""
+    KINDS = ("GronbechJensen", "Basic")
+
+    def __init__(self, kind, temperature, dt, friction, seed, is2D=False, mass=None, defaultMass=1.0, index=None):
+        assert kind in self.KINDS
+        self.lib = _lib.load()
+        self.fn = self.lib.uammd_verletnvt_gj_f64 if kind == "GronbechJensen" else self.lib.uammd_verletnvt_basic_f64
+        self.temperature, self.dt, self.friction, self.is2D = float(temperature), float(dt), float(friction), bool(is2D)
+        self.seed = int(seed) & 0xFFFFFFFF
+        self.noiseAmplitude = math.sqrt(2 * self.dt * self.friction * self.temperature)
+        self.mass, self.defaultMass, self.index, self.steps = mass, (0.0 if mass is not None else float(defaultMass)), index, 0
+
+    def integrate(self, step, pos, vel, force):
+        n = pos.shape[0] if self.index is None else self.index.shape[0]
+        check(self.fn(step, _ptr(pos), _ptr(vel), _ptr(force), _ptr(self.mass), self.defaultMass, _ptr(self.index), n, self.dt, self.friction,
+                      int(self.is2D), self.noiseAmplitude, self.steps, self.seed, _stream()))
+
+    def forwardTime(self, pos, vel, force, interactors=()):     # GronbechJensen.cu:88-115, Basic.cu:116-150
+        _check_rows(pos, 4), _check_rows(vel, 3), _check_rows(force, 4)
+        self.steps += 1
+        if self.steps == 1:
+            force.zero_()
+            for it in interactors:
+                it.sum(pos, force)
+        self.integrate(1, pos, vel, force)      # (the first half step leaves the forces at zero)
+        for it in interactors:
+            it.sum(pos, force)
+        self.integrate(2, pos, vel, force)
+
+
+class VerletNVE:
+    """VerletNVE in double (Integrator/VerletNVE.cu:133-188): half kick + drift, force reset, the interactors' forces, half kick.  The
+    velocities are the caller's (initVelocities or its own)."""
+
+    def __init__(self, dt, is2D=False, mass=None, defaultMass=1.0, index=None):
+        self.lib = _lib.load()
+        self.dt, self.is2D, self.mass, self.defaultMass, self.index, self.steps = float(dt), bool(is2D), mass, float(defaultMass), index, 0
+
+    def integrate(self, step, pos, vel, force):
+        n = pos.shape[0] if self.index is None else self.index.shape[0]
+        check(self.lib.uammd_verletnve_f64(step, _ptr(pos), _ptr(vel), _ptr(force), _ptr(self.mass), self.defaultMass, _ptr(self.index), n,
+                                           self.dt, int(self.is2D), _stream()))
+
+    def _reset_forces(self, force):             # VerletNVE.cu:152-158: the members' forces only
+        if self.index is None:
+            force.zero_()
+        else:
+            force[self.index.long()] = 0.0
+
+    def forwardTime(self, pos, vel, force, interactors=()):     # VerletNVE.cu:160-188
+        _check_rows(pos, 4), _check_rows(vel, 3), _check_rows(force, 4)
+        self.steps += 1
+        if self.steps == 1:
+            self._reset_forces(force)
+            for it in interactors:
+                it.sum(pos, force)
+        self.integrate(1, pos, vel, force)
+        self._reset_forces(force)
+        for it in interactors:
+            it.sum(pos, force)
+        self.integrate(2, pos, vel, force)
