@@ -1202,9 +1202,10 @@ int uammd_bdhi_cholesky_bdw_f64(uammd_bdhi_cholesky_f64 *h, const double *d_pos,
  *   VerletNVT GronbechJensen / Basic, initialVelocities, energy       Integrator/VerletNVT/GronbechJensen.cu:28-62, Basic.cu:12-29,86-114,173-207
  *   VerletNVE                                                         Integrator/VerletNVE.cu:64-85
  * Positions / forces are real4 = double[4N], velocities real3 = double[3N].  Every particle sums its pairs in the reference's neighbour
- * order (the 27 cells in common.cuh order, members in sorted order).  The UAMMD-shaped C++ headers do not route here yet: they refuse
- * -DDOUBLE_PRECISION as before.  Single precision only: the Verlet list, DPD / SPH / bonded / MC, the tile traversal, the fused MD
- * step, the slab drivers, num_owned ghosts and the profiling hooks.
+ * order (the 27 cells in common.cuh order, members in sorted order).  The Verlet list, the bonded kinds and DPD follow at the end of
+ * this block (verletlist_f64.hip, bonded_f64.hip, dpd_f64.hip).  The UAMMD-shaped C++ headers do not route here yet: they refuse
+ * -DDOUBLE_PRECISION as before.  Single precision only: SPH, the MC modules, the tile and ring traversals, the fused MD step, the slab
+ * drivers, num_owned ghosts and the profiling hooks.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct uammd_celllist_f64 uammd_celllist_f64; /* opaque; owns index/hash/sortPos/cellStart/cellEnd */
 /* uammd_celllist_data field for field, with double positions and box */
@@ -1265,6 +1266,61 @@ int uammd_verletnvt_initial_velocities_f64(double *d_vel, const int *d_index, do
                                            unsigned int seed, void *stream);
 int uammd_sum_kinetic_energy_f64(const double *d_vel, double *d_energy, const double *d_mass, double defaultMass, const int *d_index,
                                  int numberParticles, void *stream);
+
+/* The Verlet list in double (verletlist_f64.hip): the single-precision block argument for argument with double for every float.  The
+ * list is built on an internal uammd_celllist_f64 of the STORED positions with radius multiplier * cutOff (1.08); the test is
+ * r2 <= (multiplier * cutOff)^2 in double and the particle itself is one of its neighbours; neighbours come in the reference's order;
+ * entry k of sorted particle i is d_neighbourList[k * particleStride + i]; capacity 32 per particle, growing by 32 (the fill counts every
+ * neighbour and stores only below the capacity it was launched with); the list is rebuilt when forced, when box, cutOff or N changed, when
+ * the threshold (multiplier * cutOff - cutOff) / 2 is <= 1e-6 or when a particle drifted that far (one 4-byte read-back); sortPos is
+ * refreshed on every update.  N = 0 is a no-op; a null handle, a non-positive cut-off or a multiplier < 1 return -1 before anything is
+ * launched; a NaN position comes back as the cell list's error code. */
+typedef struct uammd_verletlist_f64 uammd_verletlist_f64;
+typedef struct {
+  const int *d_neighbourList;
+  const int *d_numberNeighbours;
+  const double *d_sortPos;  /* real4[N]: CURRENT positions in the order of the last build */
+  const int *d_groupIndex;  /* sorted index -> index in the input array */
+  int particleStride;       /* = numberParticles */
+  int maxNeighboursPerParticle;
+  int numberParticles;
+} uammd_verletlist_data_f64;
+int uammd_verletlist_create_f64(uammd_verletlist_f64 **out);
+int uammd_verletlist_destroy_f64(uammd_verletlist_f64 *h);
+int uammd_verletlist_update_f64(uammd_verletlist_f64 *h, const double *d_pos, int numberParticles, const double L[3], const int periodic[3],
+                                double cutOff, void *stream, int *rebuilt);
+int uammd_verletlist_force_next_update_f64(uammd_verletlist_f64 *h);
+int uammd_verletlist_set_cutoff_multiplier_f64(uammd_verletlist_f64 *h, double newMultiplier);
+int uammd_verletlist_get_steps_since_last_update_f64(uammd_verletlist_f64 *h, int *steps);
+int uammd_verletlist_get_f64(uammd_verletlist_f64 *h, uammd_verletlist_data_f64 *out);
+/* every listed pair through the full minimum image and the pair evaluation of uammd_lj_transverse_celllist_f64, in list order */
+int uammd_lj_transverse_verletlist_f64(uammd_verletlist_f64 *h, const uammd_lj_pair_parameters_f64 *d_paramTable, int ntypes,
+                                       const double boxL[3], const int boxPeriodic[3], double *d_force, double *d_energy, double *d_virial,
+                                       const int *d_globalIndex, void *stream);
+
+/* Bonded forces in double (bonded_f64.hip): the "Bonded interactions" block below with double for every float.  The same kinds, BondInfo
+ * order, CSR layout and two shapes (uammd_bonded_build_rows and the "bonded_wave_threshold" tunable are shared); 1.0 / sqrt(r2), acos,
+ * sin, cos and log in double.  refresh returns -1 when numberParticles is below the largest id + 1 of the uploaded set (checked on the
+ * host: the sum would read out of range); sum before an upload and a refresh returns -1; a failed upload leaves the handle as it was. */
+typedef struct uammd_bonded_f64 uammd_bonded_f64;
+int uammd_bonded_create_f64(uammd_bonded_f64 **out);
+int uammd_bonded_destroy_f64(uammd_bonded_f64 *h);
+int uammd_bonded_upload_f64(uammd_bonded_f64 *h, int kind, int nbonds, const int *ids, const double *info, int nfixed,
+                            const double *fixedPoints, const double L[3], const int periodic[3]);
+int uammd_bonded_refresh_f64(uammd_bonded_f64 *h, const int *d_id2index, int numberParticles, void *stream);
+int uammd_bonded_sum_f64(uammd_bonded_f64 *h, const double *d_pos, double *d_force, double *d_energy, double *d_virial, void *stream);
+int uammd_bonded_get_shape_f64(uammd_bonded_f64 *h, int *rows, int *entries, int *laneRows, int *waveRows);
+
+/* Potential::DPD in double (dpd_f64.hip): formula, key and truncations as documented at uammd_dpd_transverse_celllist, in double; xi is
+ * Saru's single-precision Box-Muller x promoted to double (as the thermostats above); r2 == 0 and 1/r <= 1/cutOff reject exactly.
+ * d_vel is real3[.] = double[3N] in input order.  The list variant gathers {velocity, key} into 32-byte rows in scratch memory the list
+ * handle owns and needs a list whose cells are at least cutOff wide. */
+int uammd_dpd_transverse_celllist_f64(uammd_celllist_f64 *h, const double *d_vel, const double boxL[3], const int boxPeriodic[3],
+                                      double cutOff, double A, double gamma, double sigma, unsigned long long seed, unsigned long long step,
+                                      int numberParticlesKey, double *d_force, const int *d_globalIndex, void *stream);
+int uammd_dpd_transverse_nbody_f64(const double *d_pos, const double *d_vel, int numberParticles, const double boxL[3],
+                                   const int boxPeriodic[3], double cutOff, double A, double gamma, double sigma, unsigned long long seed,
+                                   unsigned long long step, int numberParticlesKey, double *d_force, const int *d_globalIndex, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bonded interactions.  Replaces BondedForces<BondType, particlesPerBond> (Interactor/BondedForces.{cuh,cu}),

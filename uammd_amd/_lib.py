@@ -463,6 +463,23 @@ SIGNATURES = {
     "uammd_verletnve_f64": (_i, [_i, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _i, _vp]),
     "uammd_verletnvt_initial_velocities_f64": (_i, [_vp, _vp, _d, _i, _i, _u, _vp]),
     "uammd_sum_kinetic_energy_f64": (_i, [_vp, _vp, _vp, _d, _vp, _i, _vp]),
+    # path A in double: Verlet list, bonded forces, DPD (verletlist_f64.hip, bonded_f64.hip, dpd_f64.hip)
+    "uammd_verletlist_create_f64": (_i, [C.POINTER(_vp)]),
+    "uammd_verletlist_destroy_f64": (_i, [_vp]),
+    "uammd_verletlist_update_f64": (_i, [_vp, _vp, _i, _d3, _i3, _d, _vp, C.POINTER(_i)]),
+    "uammd_verletlist_force_next_update_f64": (_i, [_vp]),
+    "uammd_verletlist_set_cutoff_multiplier_f64": (_i, [_vp, _d]),
+    "uammd_verletlist_get_steps_since_last_update_f64": (_i, [_vp, C.POINTER(_i)]),
+    "uammd_verletlist_get_f64": (_i, [_vp, C.POINTER(VerletListData)]),
+    "uammd_lj_transverse_verletlist_f64": (_i, [_vp, _vp, _i, _d3, _i3, _vp, _vp, _vp, _vp, _vp]),
+    "uammd_bonded_create_f64": (_i, [C.POINTER(_vp)]),
+    "uammd_bonded_destroy_f64": (_i, [_vp]),
+    "uammd_bonded_upload_f64": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _d3, _i3]),
+    "uammd_bonded_refresh_f64": (_i, [_vp, _vp, _i, _vp]),
+    "uammd_bonded_sum_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "uammd_bonded_get_shape_f64": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "uammd_dpd_transverse_celllist_f64": (_i, [_vp, _vp, _d3, _i3, _d, _d, _d, _d, C.c_ulonglong, C.c_ulonglong, _i, _vp, _vp, _vp]),
+    "uammd_dpd_transverse_nbody_f64": (_i, [_vp, _vp, _i, _d3, _i3, _d, _d, _d, _d, C.c_ulonglong, C.c_ulonglong, _i, _vp, _vp, _vp]),
 }
 
 MATVEC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)

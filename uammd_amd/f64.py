@@ -324,7 +324,7 @@ class BD:
             self._advance(pos, 0, original_index if self.scheme == 3 else None)
 
 
-# ---- path A in double (md_f64.hip): cell list, Lennard-Jones, Verlet integrators ------------------------------------------------------
+# ---- path A in double (md_f64.hip, verletlist_f64.hip, bonded_f64.hip, dpd_f64.hip): neighbour lists, LJ, bonds, DPD, Verlet integrators -----
 class Box:
     """Box (utils/Box.cuh) with double sides."""
 
@@ -461,13 +461,81 @@ class LJ:
         return self._dev
 
 
-class PairForcesLJ:
-    """PairForces<Potential::LJ, CellList> in double (PairForces.cu:43-78): the cell list unless the box is at most 3 cut-offs in every
-    direction, then all pairs.  sum() ACCUMULATES into the arrays it is given (Transverser::set does +=)."""
+class VerletList:
+    """The NeighbourList concept on double positions [N, 4] over the Verlet list (uammd_verletlist_*_f64): update(box, cutoff, pos) +
+    getVerletList + transverse_lj.  No ParticleData behind it: every update looks at the positions it is given (the drift check decides
+    whether the list is rebuilt)."""
 
-    def __init__(self, box, potential, algo=0):
+    def __init__(self):
         self.lib = _lib.load()
-        self.box, self.pot, self.algo, self.nl = box, potential, algo, None
+        h = C.c_void_p()
+        check(self.lib.uammd_verletlist_create_f64(C.byref(h)))
+        self.h = h
+        self.N = 0
+        self.rebuilds = 0
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.uammd_verletlist_destroy_f64(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def forceNextUpdate(self):
+        check(self.lib.uammd_verletlist_force_next_update_f64(self.h))
+
+    def setCutOffMultiplier(self, multiplier):
+        check(self.lib.uammd_verletlist_set_cutoff_multiplier_f64(self.h, float(multiplier)))
+
+    def getNumberOfStepsSinceLastUpdate(self):
+        steps = C.c_int()
+        check(self.lib.uammd_verletlist_get_steps_since_last_update_f64(self.h, C.byref(steps)))
+        return steps.value
+
+    def update(self, box, cutoff, pos):
+        """VerletListBase::update (VerletListBase.cuh:107-117); returns whether the list was rebuilt."""
+        _check_rows(pos, 4)
+        rebuilt = C.c_int(0)
+        self._pos_ref = pos
+        check(self.lib.uammd_verletlist_update_f64(self.h, _ptr(pos), pos.shape[0], _d3(box.boxSize), _i3([int(p) for p in box.periodic]),
+                                                   float(cutoff), _stream(), C.byref(rebuilt)))
+        self.N = pos.shape[0]
+        self.rebuilds += rebuilt.value
+        return bool(rebuilt.value)
+
+    def getVerletList(self):
+        d = _lib.VerletListData()
+        check(self.lib.uammd_verletlist_get_f64(self.h, C.byref(d)))
+        return d
+
+    def to_host(self):
+        """Copies the list to numpy (tests): neighbourList[capacity, N] (entry k of sorted particle i at [k, i]), numberNeighbours,
+        sortPos, groupIndex."""
+        d = self.getVerletList()
+        n, cap = d.numberParticles, d.maxNeighboursPerParticle
+        torch.cuda.synchronize()
+        w = CellList._wrap
+        return dict(neighbourList=w(d.d_neighbourList, (cap, n), torch.int32).cpu().numpy(),
+                    numberNeighbours=w(d.d_numberNeighbours, (n,), torch.int32).cpu().numpy(),
+                    sortPos=w(d.d_sortPos, (n, 4), torch.float64).cpu().numpy(),
+                    groupIndex=w(d.d_groupIndex, (n,), torch.int32).cpu().numpy(),
+                    maxNeighboursPerParticle=cap, particleStride=d.particleStride, numberParticles=n)
+
+    def transverse_lj(self, param_table, ntypes, box, force=None, energy=None, virial=None, global_index=None, algo=0):
+        check(self.lib.uammd_lj_transverse_verletlist_f64(self.h, _ptr(param_table), int(ntypes), _d3(box.boxSize),
+                                                          _i3([int(p) for p in box.periodic]), _ptr(force), _ptr(energy), _ptr(virial),
+                                                          _ptr(global_index), _stream()))
+
+
+class PairForcesLJ:
+    """PairForces<Potential::LJ, NeighbourList> in double (PairForces.cu:43-78): the neighbour list (a CellList unless nl=VerletList() is
+    given) unless the box is at most 3 cut-offs in every direction, then all pairs.  sum() ACCUMULATES into the arrays it is given
+    (Transverser::set does +=)."""
+
+    def __init__(self, box, potential, algo=0, nl=None):
+        self.lib = _lib.load()
+        self.box, self.pot, self.algo, self.nl = box, potential, algo, nl
 
     def sum(self, pos, force=None, energy=None, virial=None):
         _check_rows(pos, 4)
@@ -483,6 +551,100 @@ class PairForcesLJ:
             self.nl = CellList()
         self.nl.update(self.box, rc, pos)
         self.nl.transverse_lj(tbl, self.pot.ntypes, self.box, force, energy, virial, None, self.algo)
+
+
+class BondedForces:
+    """BondedForces / AngularBondedForces / TorsionalBondedForces in double (uammd_bonded_*_f64).  kind: "harmonic", "fene", "angular",
+    "torsional" or "fourier"; ids int[nbonds, members] (a negative id -(j+1) names fixedPoints[j], two-member kinds only); info
+    double[nbonds, 2] in the bond file's order ("k p0"); box: the kind's Box (None: no minimum image).  refresh(id2index) follows a
+    reordering of the particles and has to be called once before the first sum."""
+    KINDS = {"harmonic": (0, 2, False), "fene": (1, 2, True), "angular": (2, 3, True), "torsional": (3, 4, True), "fourier": (4, 4, True)}
+
+    def __init__(self, kind, ids, info, box=None, fixedPoints=None):
+        self.lib = _lib.load()
+        self.kind, self.members, swap = self.KINDS[kind]
+        self.box = box if box is not None else Box(0.0, (False, False, False))
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, self.members))
+        info = np.asarray(info, np.float64).reshape(-1, 2)
+        if info.shape[0] != ids.shape[0]:
+            raise ValueError("one BondInfo per bond")
+        fixedPoints = np.zeros((0, 4)) if fixedPoints is None else np.asarray(fixedPoints, np.float64)
+        fp = np.zeros((fixedPoints.shape[0], 4), np.float64)
+        fp[:, :fixedPoints.shape[1]] = fixedPoints
+        structInfo = np.ascontiguousarray(info[:, ::-1] if swap else info)      # BondInfo order: {k, r0} for Harmonic, {p0, k} otherwise
+        self.nbonds = ids.shape[0]
+        h = C.c_void_p()
+        check(self.lib.uammd_bonded_create_f64(C.byref(h)))
+        self.h = h
+        check(self.lib.uammd_bonded_upload_f64(self.h, self.kind, self.nbonds, ids.ctypes.data_as(C.c_void_p),
+                                               structInfo.ctypes.data_as(C.c_void_p), fp.shape[0], fp.ctypes.data_as(C.c_void_p),
+                                               _d3(self.box.boxSize), _i3([int(p) for p in self.box.periodic])))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                torch.cuda.synchronize()
+                self.lib.uammd_bonded_destroy_f64(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def refresh(self, id2index):
+        """id2index int32[N] on the device: the current index of the particle with each id (ParticleData::getIdOrderedIndices)."""
+        assert id2index.dtype == torch.int32 and id2index.is_contiguous()
+        check(self.lib.uammd_bonded_refresh_f64(self.h, _ptr(id2index), id2index.shape[0], _stream()))
+
+    def shape(self):
+        """(rows, entries, rows on the lane-per-row shape, rows on the wave-per-row shape)."""
+        r, e, lr, wr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.uammd_bonded_get_shape_f64(self.h, C.byref(r), C.byref(e), C.byref(lr), C.byref(wr)))
+        return r.value, e.value, lr.value, wr.value
+
+    def sum(self, pos, force=None, energy=None, virial=None):
+        _check_rows(pos, 4)
+        check(self.lib.uammd_bonded_sum_f64(self.h, _ptr(pos), _ptr(force), _ptr(energy), _ptr(virial), _stream()))
+
+
+class PairForcesDPD:
+    """PairForces<Potential::DPD> in double (DPD.cuh:121-170, PairForces.cu:43-68): sum(pos, vel, force) ACCUMULATES the DPD pair force.
+    sigma = sqrt(2 kT) / sqrt(dt) in double (DPD.cuh:69); the step advances once per sum; the cell list when the box exceeds 3 cut-offs
+    in every periodic direction, else all pairs."""
+    needs_velocities = True      # the integrators call sum(pos, vel, force)
+
+    def __init__(self, box, cutOff=1.0, A=1.0, gamma=1.0, temperature=0.0, dt=0.0, seed=0):
+        self.lib = _lib.load()
+        self.box, self.rcut, self.A, self.gamma = box, float(cutOff), float(A), float(gamma)
+        self.temperature, self.dt, self.seed = float(temperature), float(dt), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.sigma = math.sqrt(2.0 * self.temperature) / math.sqrt(self.dt) if self.dt > 0 else (0.0 if self.temperature == 0 else float("inf"))
+        self.step = 0
+        self.nl = None
+
+    def uses_cell_list(self):
+        L = self.box.boxSize
+        return all(L[k] > 3 * self.rcut for k in range(3) if self.box.periodic[k])
+
+    def sum(self, pos, vel, force, global_index=None):
+        _check_rows(pos, 4), _check_rows(vel, 3), _check_rows(force, 4)
+        self.step += 1
+        L, per = _d3(self.box.boxSize), _i3([int(p) for p in self.box.periodic])
+        args = (self.rcut, self.A, self.gamma, self.sigma, self.seed, self.step, pos.shape[0], _ptr(force), _ptr(global_index), _stream())
+        if self.uses_cell_list():
+            if self.nl is None:
+                self.nl = CellList()
+            members = pos if global_index is None else pos[global_index.long()].contiguous()      # the list is built on the members
+            self.nl.update(self.box, self.rcut, members)
+            check(self.lib.uammd_dpd_transverse_celllist_f64(self.nl.h, _ptr(vel), L, per, *args))
+        else:
+            n = pos.shape[0] if global_index is None else global_index.shape[0]
+            check(self.lib.uammd_dpd_transverse_nbody_f64(_ptr(pos), _ptr(vel), n, L, per, *args))
+
+
+def _sum_interactors(interactors, pos, vel, force):
+    for it in interactors:
+        if getattr(it, "needs_velocities", False):
+            it.sum(pos, vel, force)
+        else:
+            it.sum(pos, force)
 
 
 def initVelocities(vel, velAmplitude, seed, is2D=False, index=None):
@@ -524,11 +686,9 @@ class VerletNVT:
         self.steps += 1
         if self.steps == 1:
             force.zero_()
-            for it in interactors:
-                it.sum(pos, force)
+            _sum_interactors(interactors, pos, vel, force)
         self.integrate(1, pos, vel, force)      # (the first half step leaves the forces at zero)
-        for it in interactors:
-            it.sum(pos, force)
+        _sum_interactors(interactors, pos, vel, force)
         self.integrate(2, pos, vel, force)
 
 
@@ -556,10 +716,8 @@ class VerletNVE:
         self.steps += 1
         if self.steps == 1:
             self._reset_forces(force)
-            for it in interactors:
-                it.sum(pos, force)
+            _sum_interactors(interactors, pos, vel, force)
         self.integrate(1, pos, vel, force)
         self._reset_forces(force)
-        for it in interactors:
-            it.sum(pos, force)
+        _sum_interactors(interactors, pos, vel, force)
         self.integrate(2, pos, vel, force)
